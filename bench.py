@@ -6,7 +6,14 @@ tekkaman.cgltrace, 1024x1024, one primary ray per pixel (raster-exact, from
 the per-8x8-block candidate lists built on the device) + one any-hit shadow
 ray per geometry hit (ballot/mbcnt-compacted into full waves, each lane
 scanning its light-space cell list -- the cube map of triangle lists around
-the point light, built on the device -- nearest to the light first).  Timed beside it in the same command, each
+the point light, built on the device -- nearest to the light first).
+
+A plain run (`--gpus 1 --steps N --warmup W`) does what `value` needs and no
+more: scene, tree and configure, the instrumented frame that counts the rays
+of a frame, the clock ramp, W + N frames, `--dump-outputs DIR` if given, the
+result line.  `--full` adds everything else the benchmark measures: the
+kernel clock and the rooflines of `value`, the BVH rebuild and cold configure
+probes, the CPU baseline, and, timed beside `value` in the same command, each
 with its own kernel clock, roofline and PMC record (`series`): the same frame
 by BVH traversal only (binary16 BVH4 wave-packet walks; series.bvh_walk),
 config 4's 4-bounce path trace (series.path), config 2's 256^2 flat list
@@ -27,8 +34,18 @@ GPUs"; per GPU in config.mrays_per_s_per_gpu).  `--gpus N` without
 WORLD_SIZE launches the N ranks itself (torch.distributed.run, before
 anything touches a GPU).  The communicator's start and the first gathers
 run under a watchdog (BENCH_DIST_TIMEOUT_S, default 240 s): a hang ends the
-rank with a message and the tracebacks on stderr.  The line also carries
-series.weak_1024_sqrtN (~1M pixels per GPU).
+rank with a message and the tracebacks on stderr.  With `--full` the line
+also carries series.weak_1024_sqrtN (~1M pixels per GPU) and the render /
+exchange split of a step.
+
+`--dump-outputs DIR`: after the timed steps rank 0 writes the frame the last
+timed step left -- what a caller of the timed path reads back -- as
+DIR/framebuffer.npy, float32 [H, W, 4]: the bytes of each pixel word in memory
+order (B, G, R, A), exact.  A frame above DUMP_MAX_PIXELS is written as a
+fixed, seeded sample of its pixels, float32 [n, 4], with the sampled pixel
+indices (y * W + x) in DIR/framebuffer_index.npy (float64).  The scene, the
+light and the size are fixed by the arguments, so two builds write frames
+that can be compared value for value.
 
 Rank 0 prints one JSON line.  Everything else goes to stderr.
 """
@@ -61,10 +78,32 @@ NODE4H_BYTES = 64      # BVH4 node with binary16 planes (rt_node4h_t): 48 B of p
 # at the 2.4 GHz peak engine clock
 VALU_ISSUE_PEAK_GIPS = 1024 * 2.4 / 2.0
 CONFIG5_SIDE = 4096    # BASELINE config 5
+# --dump-outputs: a frame up to 2^21 pixels is written whole (32 MB of
+# float32), a larger one as 2^21 sampled pixels + their indices (48 MB)
+DUMP_MAX_PIXELS = 1 << 21
 
 
 def log(*a):
     print(*a, file=sys.stderr, flush=True)
+
+
+def dump_outputs(out_dir: str, frame: np.ndarray, width: int, height: int) -> dict:
+    """Write the uint32 frame (height * width pixel words) under out_dir as
+    float32 channel values (module docstring); returns what was written."""
+    os.makedirs(out_dir, exist_ok=True)
+    words = np.ascontiguousarray(frame, dtype=np.uint32).reshape(-1)
+    assert words.size == width * height, (words.size, width, height)
+    index = None
+    if words.size > DUMP_MAX_PIXELS:
+        index = np.sort(np.random.default_rng(0).choice(words.size, DUMP_MAX_PIXELS, replace=False))
+        words = words[index]
+    chan = words.view(np.uint8).reshape(-1, 4).astype(np.float32)
+    if index is None:
+        chan = chan.reshape(height, width, 4)
+    else:
+        np.save(os.path.join(out_dir, "framebuffer_index.npy"), index.astype(np.float64))
+    np.save(os.path.join(out_dir, "framebuffer.npy"), chan)
+    return {"dir": out_dir, "framebuffer": list(chan.shape), "sampled": index is not None}
 
 
 def algorithmic_bytes(st: dict, pixels: int, node_bytes: int = NODE_BYTES) -> int:
@@ -635,12 +674,20 @@ def main():
     ap.add_argument("--size", type=int, default=None,
                     help="frame side (default: 1024 at N=1, config 3; 4096 at N>1, config 5)")
     ap.add_argument("--no-shadows", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline figure: the kernel clock and rooflines, the "
+                         "series (other configs, BVH walk, moving light, scaling points), the BVH "
+                         "rebuild and cold configure probes, the N>1 render / exchange split, the "
+                         "CPU baseline; the --no-* / --series / --cpu-budget options below trim it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last timed step's frame to "
+                         "DIR/framebuffer.npy (float32 channel values)")
     ap.add_argument("--cpu-budget", type=float, default=15.0)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-series", action="store_true",
-                    help="skip the strong/weak scaling series runs (default at N>1)")
+                    help="--full: skip the strong/weak scaling series runs (default at N>1)")
     ap.add_argument("--series", action="store_true",
-                    help="N=1: also run the weak-scaling series point (~1024^2 sqrt(N))")
+                    help="--full, N=1: also run the weak-scaling series point (~1024^2 sqrt(N))")
     ap.add_argument("--workload", choices=("shadow", "path", "flat"), default="shadow",
                     help="shadow: BASELINE config 3 (the metric's config, default); "
                          "path: config 4, 4-bounce diffuse path trace; "
@@ -726,9 +773,11 @@ def main():
     r = rt.Renderer(scene)
     bvh_st = r.bvh_stats()  # the renderer's tree, built on the device at creation
     bvh_first_ms = bvh_st["build_ms"]  # including the build image's first load
-    # the same build again (image resident): best of 3, before the renderer is configured
-    bvh_rebuild_ms = min(r.build_bvh("sah")["build_ms"] for _ in range(3)) if bvh_st["method"] == 1 else None
-    bvh_st = r.bvh_stats()
+    # --full: the same build again (image resident): best of 3, before the renderer is configured
+    bvh_rebuild_ms = None
+    if args.full and bvh_st["method"] == 1:
+        bvh_rebuild_ms = min(r.build_bvh("sah")["build_ms"] for _ in range(3))
+        bvh_st = r.bvh_stats()
 
     def make_run(s, bvh_walk=False, m=None, gather=None):
         m = m or mode
@@ -748,7 +797,8 @@ def main():
     # (~5 ms) whatever --steps is: a steadier figure than a few frames, and
     # the device reaches its working clocks before the timed region instead
     # of inside it (at the driver's --steps 20 --warmup 5: 62.3-62.5 Grays/s
-    # after 20 of them, 64.2-64.3 after 200 -- DESIGN 6, r05at)
+    # after 20 of them, 64.2-64.3 after 200 -- DESIGN 6, r05at).  They are
+    # that ramp, ~5 ms, so a plain run keeps them: `value` depends on them
     sync_ms = None
     sync_n = 0
     if not use_gather:
@@ -767,23 +817,30 @@ def main():
     dog.arm("the timed steps (render + RCCL gather)")
     elapsed = run.timed(args.steps, args.warmup, dist)
     dog.disarm()
-    # the kernel's average duration: HIP events around a back-to-back run of
-    # the same frames on the driver's stream (Run.kernel_clock)
+    # --dump-outputs: the frame the last timed step left (rank 0; N > 1: the
+    # frame assembled from the last step's gather)
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        frame = run.fg.image.cpu().numpy().view(np.uint32) if run.fg is not None else r.framebuffer()
+        dumped = dump_outputs(args.dump_outputs, frame, side, side)
+        log(f"bench.py: wrote {dumped['framebuffer']} to {args.dump_outputs}/framebuffer.npy")
+    # --full: the kernel's average duration: HIP events around a back-to-back
+    # run of the same frames on the driver's stream (Run.kernel_clock)
     # (at least 200 frames after 20 untimed ones: at the driver's 20-step
     # command a 50-frame clock of a 0.03 ms frame is a 1.5 ms burst that
     # still runs below the device's working clock)
     clock_frames = max(200, min(args.steps, 1000))
     clock_warmup = 20
-    avg_kernel_ms = run.kernel_clock(clock_frames, clock_warmup)
+    avg_kernel_ms = run.kernel_clock(clock_frames, clock_warmup) if args.full else None
     st = r.stats()
     elapsed, rays_total = reduce_max_sum(dist, coll_dev, elapsed, run.rays_local)
     ms_per_step = elapsed / args.steps * 1e3
     value = rays_total * args.steps / elapsed / 1e6
-    # N > 1: the same steps with only the render, and with only the frame
-    # exchange (gather of the last frame + assembly), max over ranks -- which
-    # half sets the step time at this N
+    # --full, N > 1: the same steps with only the render, and with only the
+    # frame exchange (gather of the last frame + assembly), max over ranks --
+    # which half sets the step time at this N
     split = None
-    if use_gather:
+    if use_gather and args.full:
         split_steps = max(20, min(args.steps, 500))
         e_r = run.timed(split_steps, 5, dist, exchange=False)
         e_x = run.timed(split_steps, 5, dist, render=False)
@@ -828,14 +885,14 @@ def main():
 
     # N > 1: config 5's frame on these N GPUs is `value` itself; the weak
     # point (~1M pixels per GPU) beside it.  N = 1 (`--series`): the weak point
-    if not args.no_series and not flat and (n_gpus > 1 or args.series):
+    if args.full and not args.no_series and not flat and (n_gpus > 1 or args.series):
         if side == CONFIG5_SIDE:
             series["strong_4096"] = {"side": side, "value": round(value, 3),
                                      "ms_per_step": round(ms_per_step, 5), "same_as": "value"}
         s = frame_side(n_gpus, 1024)
         if s != side:
             timed_series("weak_1024_sqrtN", s, mode, "rt_kernel (entry vx_main_rt_kernel)")
-    extra = n_gpus == 1 and not args.no_bvh_series
+    extra = args.full and n_gpus == 1 and not args.no_bvh_series
     if extra and mode == "shadow" and shadows:
         # BASELINE config 3 by BVH traversal only (RT_RENDER_BVH_WALK, image
         # rt_bvh: primary visibility by the binary16-BVH4 packet walk, shadow
@@ -899,13 +956,17 @@ def main():
     images = None
     if path and setup_st.get("path_queue"):
         images = ("pt_primary.co", "pt_queue.co")  # the two-kernel form (RT_PT_QUEUE=1)
-    roof, issue = make_roofline(inst, avg_kernel_ms, mode, side, node_bytes, images, n_gpus)
+    # --full: the rooflines divide by the kernel clock
+    roof = issue = None
+    if args.full:
+        roof, issue = make_roofline(inst, avg_kernel_ms, mode, side, node_bytes, images, n_gpus)
     info = scene.info()  # (after the timed region: parse time, host-side counts)
     out = {
         "metric": metric,
         "value": round(value, 3),
         "unit": "Mrays/s",
         "n_gpus": n_gpus,
+        "full": args.full,
         "steps": args.steps,
         "warmup": args.warmup,
         "ms_per_step": round(ms_per_step, 5),
@@ -951,15 +1012,18 @@ def main():
             "grid": st["grid"], "block": st["block"],
             "rays_per_frame": int(rays_total),
             "mrays_per_s_per_gpu": round(value / n_gpus, 3),
-            "kernel_ms": round(avg_kernel_ms, 5),
+            "kernel_ms": round(avg_kernel_ms, 5) if args.full else None,
             "frames": "back to back (vx_start queues behind the in-flight frames; no per-launch "
-                      "events in the timed region); kernel_ms = two HIP events on the driver's "
-                      f"stream around {clock_frames} such frames after the "
-                      "timed region / frames (render only)",
+                      "events in the timed region)"
+                      + ("; kernel_ms = two HIP events on the driver's "
+                         f"stream around {clock_frames} such frames after the "
+                         "timed region / frames (render only)" if args.full else
+                         "; kernel_ms and the rooflines: --full"),
             "sync_ms_per_step": round(sync_ms, 5) if sync_ms is not None else None,
             "sync_frames": (f"{sync_n} synchronous frames (vx_start + vx_ready_wait each), host "
                             "clock, before the timed region") if sync_ms is not None else None,
-            "kernel_mrays_per_s": round(run.rays_local / (avg_kernel_ms * 1e-3) / 1e6, 3),
+            "kernel_mrays_per_s": (round(run.rays_local / (avg_kernel_ms * 1e-3) / 1e6, 3)
+                                   if args.full else None),
             "counters": "off in the timed frames (rays per frame from the instrumented pre-run)",
         },
         "series": series,
@@ -972,7 +1036,9 @@ def main():
         out["config"]["gather_verified"] = gather_ok
     if split is not None:
         out["config"]["step_split"] = split
-    if n_gpus == 1 and not args.no_cpu_baseline:
+    if dumped is not None:
+        out["dump_outputs"] = dumped
+    if args.full and n_gpus == 1 and not args.no_cpu_baseline:
         try:
             out["cpu_baseline"] = cpu_baseline(shadows, side, light, args.cpu_budget, path,
                                                args.bounces, flat, r.bvh4)

@@ -3,8 +3,9 @@
 (the headline must be reproducible from profiles/ for the
 image actually timed).
 
-Inputs: the bench JSON line (bench.py's stdout, or the driver's BENCH_rNN.json
-whose `parsed` holds it), the rocprofv3 --kernel-trace --stats summary of the
+Inputs: the bench JSON line (the stdout of bench.py --full, which carries the
+kernel clock, rooflines and series, or a BENCH_rNN.json whose `parsed` holds
+such a line), the rocprofv3 --kernel-trace --stats summary of the
 same command (<prefix>_kernel_stats.csv: one row per kernel name; every
 image's entry is vx_main_<image>, so the timed kernel is its own row), and
 the PMC record the line cites (profiles/pmc_<mode>.json).

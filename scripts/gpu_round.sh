@@ -19,10 +19,13 @@ step "pmc $m"; MODE=$m TAG=${T}_pmc bash scripts/pmc_profile.sh > gpurun_out/${T
 cp gpurun_out/${T}_pmc/pmc_$m.json profiles/
 done
 fi
-step "bench"; timeout -k 10 300 python bench.py > gpurun_out/${T}_bench.json 2> gpurun_out/${T}_bench.err; rc=$?; cat gpurun_out/${T}_bench.json; tail -2 gpurun_out/${T}_bench.err; [ $rc -eq 0 ] || exit $rc
-step "bench path"; timeout -k 10 300 python bench.py --workload path --cpu-budget 5 > gpurun_out/${T}_bench_path.json 2> gpurun_out/${T}_bench_path.err; rc=$?; cat gpurun_out/${T}_bench_path.json; tail -2 gpurun_out/${T}_bench_path.err; [ $rc -eq 0 ] || exit $rc
-step "bench flat"; timeout -k 10 300 python bench.py --workload flat --cpu-budget 5 > gpurun_out/${T}_bench_flat.json 2> gpurun_out/${T}_bench_flat.err; rc=$?; cat gpurun_out/${T}_bench_flat.json; tail -2 gpurun_out/${T}_bench_flat.err; [ $rc -eq 0 ] || exit $rc
-step "rocprof"; timeout -k 10 300 rocprofv3 --kernel-trace --stats -d gpurun_out/${T}_prof -o ${T} --output-format csv -- python3 bench.py --no-cpu-baseline > gpurun_out/${T}_prof.log 2>&1; rc=$?; tail -1 gpurun_out/${T}_prof.log; [ $rc -eq 0 ] || exit $rc
-step "rocprof path"; timeout -k 10 300 rocprofv3 --kernel-trace --stats -d gpurun_out/${T}_prof_path -o ${T}_path --output-format csv -- python3 bench.py --no-cpu-baseline --workload path > gpurun_out/${T}_prof_path.log 2>&1; rc=$?; tail -1 gpurun_out/${T}_prof_path.log; [ $rc -eq 0 ] || exit $rc
-step "rocprof flat"; timeout -k 10 300 rocprofv3 --kernel-trace --stats -d gpurun_out/${T}_prof_flat -o ${T}_flat --output-format csv -- python3 bench.py --no-cpu-baseline --workload flat > gpurun_out/${T}_prof_flat.log 2>&1; rc=$?; tail -1 gpurun_out/${T}_prof_flat.log; [ $rc -eq 0 ] || exit $rc
+# the bench lines and their rocprofv3 summaries (bench.py --full: kernel clock,
+# rooflines, series, CPU baseline) go under $OUT, default bench_out/
+OUT=${OUT:-bench_out}; mkdir -p "$OUT"
+step "bench"; timeout -k 10 300 python bench.py --full > "$OUT/${T}_bench.json" 2> "$OUT/${T}_bench.err"; rc=$?; cat "$OUT/${T}_bench.json"; tail -2 "$OUT/${T}_bench.err"; [ $rc -eq 0 ] || exit $rc
+step "bench path"; timeout -k 10 300 python bench.py --full --workload path --cpu-budget 5 > "$OUT/${T}_bench_path.json" 2> "$OUT/${T}_bench_path.err"; rc=$?; cat "$OUT/${T}_bench_path.json"; tail -2 "$OUT/${T}_bench_path.err"; [ $rc -eq 0 ] || exit $rc
+step "bench flat"; timeout -k 10 300 python bench.py --full --workload flat --cpu-budget 5 > "$OUT/${T}_bench_flat.json" 2> "$OUT/${T}_bench_flat.err"; rc=$?; cat "$OUT/${T}_bench_flat.json"; tail -2 "$OUT/${T}_bench_flat.err"; [ $rc -eq 0 ] || exit $rc
+step "rocprof"; timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$OUT/${T}_prof" -o ${T} --output-format csv -- python3 bench.py --full --no-cpu-baseline > "$OUT/${T}_prof.log" 2>&1; rc=$?; tail -1 "$OUT/${T}_prof.log"; [ $rc -eq 0 ] || exit $rc
+step "rocprof path"; timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$OUT/${T}_prof_path" -o ${T}_path --output-format csv -- python3 bench.py --full --no-cpu-baseline --workload path > "$OUT/${T}_prof_path.log" 2>&1; rc=$?; tail -1 "$OUT/${T}_prof_path.log"; [ $rc -eq 0 ] || exit $rc
+step "rocprof flat"; timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$OUT/${T}_prof_flat" -o ${T}_flat --output-format csv -- python3 bench.py --full --no-cpu-baseline --workload flat > "$OUT/${T}_prof_flat.log" 2>&1; rc=$?; tail -1 "$OUT/${T}_prof_flat.log"; [ $rc -eq 0 ] || exit $rc
 if [ -n "$AB" ]; then step "ab"; timeout -k 10 250 python scripts/ab_variants.py --rounds 8 --variants "$AB" > gpurun_out/${T}_ab.json 2> gpurun_out/${T}_ab.err; rc=$?; cat gpurun_out/${T}_ab.json; exit $rc; fi
