@@ -275,6 +275,8 @@ int rt_renderer_set_list_policy(rt_renderer_h r, uint32_t defer_frames);
 #define RT_REC_BLIST 11u    /* rt_bentry_t per list entry (+3 padding entries, RT_BLIST_PAD) */
 #define RT_REC_SIDX 12u     /* uint32[2] per light-space cell: first entry, count */
 #define RT_REC_SLIST 13u    /* rt_tri_t per light-space list entry (+1 padding record) */
+#define RT_REC_CDESC 14u    /* rt_cdesc_t per chunk of the whole-block tier, as the device setup built it */
+#define RT_REC_CDESC_HOST 15u /* the same table restated on the host from the work order and list headers */
 int rt_renderer_export_records(rt_renderer_h r, uint32_t which, void* out, uint64_t bytes,
                                uint64_t* size);
 

@@ -37,6 +37,8 @@ def main():
     ap.add_argument("--size", type=int, default=1024)
     ap.add_argument("--rounds", type=int, default=10)
     ap.add_argument("--frames", type=int, default=10)
+    ap.add_argument("--warmup-rounds", type=int, default=0,
+                    help="rounds run first and not recorded (the clocks settle over the first rounds)")
     ap.add_argument("--scene", default=os.path.join(ROOT, "tests/golden/scenes/tekkaman.cgltrace"))
     ap.add_argument("--variants", default="")
     ap.add_argument("--no-shadows", action="store_true")
@@ -79,7 +81,9 @@ def main():
     times = {n: [] for n in names}
     sync = {n: [] for n in names}
     host = {n: [] for n in names}
-    for _ in range(args.rounds):
+    for rnd in range(args.warmup_rounds + args.rounds):
+        if rnd == args.warmup_rounds:  # the recorded rounds start here
+            times, sync, host = ({n: [] for n in names} for _ in range(3))
         for n in names:
             r = rs[n]
             # back-to-back frames (no per-launch events, the bench's kernel
@@ -93,6 +97,8 @@ def main():
                 r.render()
             host[n].append((time.perf_counter() - t0) / 10 * 1e3)
     out = {n: {"median_ms": round(float(np.median(t)), 5), "min_ms": round(float(np.min(t)), 5),
+               "range_ms": round(float(np.max(t) - np.min(t)), 5),  # round-to-round, this variant
+               "rounds_ms": [round(float(x), 5) for x in t],
                "sync_median_ms": round(float(np.median(sync[n])), 5),
                "sync_host_median_ms": round(float(np.median(host[n])), 5),
                "grid": rs[n].stats()["grid"]} for n, t in times.items()}

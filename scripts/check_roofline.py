@@ -114,7 +114,20 @@ def main():
             sys.exit(f"{k} not in {a.stats} (names: {sorted(rows)})")
     # a frame's device time: the sum of its kernels' average durations
     dur_s = sum(float(rows[k]["AverageNs"]) for k in knames) * 1e-9
-    pmc = json.load(open(a.pmc or f"profiles/pmc_{mode}.json"))
+    # A round's evidence directory keeps the PMC records of the images its
+    # bench line was taken on (<round>/pmc/, beside <round>/final/ and
+    # <round>/prof/): the line is checked against those, not against
+    # profiles/pmc_*.json, which follow the images the tree builds now.
+    snap = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(a.bench))), "pmc")
+
+    used = []  # the record files read, reported in the output
+
+    def record(path):
+        own = os.path.join(snap, os.path.basename(path))
+        used.append(os.path.relpath(own) if os.path.exists(own) else path)
+        return used[-1]
+
+    pmc = json.load(open(a.pmc or record(f"profiles/pmc_{mode}.json")))
     rf = line["roofline"]
     out = {"kernel": "+".join(knames), "rocprof_calls": [int(rows[k]["Calls"]) for k in knames],
            "rocprof_avg_ms": round(dur_s * 1e3, 5),
@@ -183,7 +196,7 @@ def main():
         br = sb["roofline"]
         src = br.get("pmc_source") or (sb.get("roofline_issue") or {}).get("source", "").split(" ")[0]
         try:
-            pb = json.load(open(src)) if src else None
+            pb = json.load(open(record(src))) if src else None
         except OSError:
             pb = None
         if br.get("bound") == "hbm":
@@ -197,6 +210,7 @@ def main():
             check(f"series.{name}.roofline_issue.frac", pb["sq"]["SQ_INSTS_VALU"] / db / 1e9 / VALU_ISSUE_PEAK_GIPS,
                   bi["frac"])
     out["ok"] = ok
+    out["pmc_records"] = sorted(set(used)) if not a.pmc else [a.pmc]
     print(json.dumps(out, indent=1))
     sys.exit(0 if ok else 1)
 

@@ -477,6 +477,46 @@ int device_setup(rt_renderer* r, bool raster, bool order_on, bool lists, bool sl
   return 0;
 }
 
+int chunk_desc(rt_renderer* r, uint32_t* launches) {
+  rt_kernel_arg_t& a = r->arg;
+  a.cdesc_addr = 0;
+  a.cdesc_first = 0;
+  r->cdesc_n = 0;
+  // the record packs pixel coordinates, the row pitch and the list length in 16 bits each
+  if (a.width > 0xffffu || a.height > 0xffffu || (a.blist_blocks && r->setup.blist_max > 0xffffu) ||
+      a.split_tiles > r->local_tiles)
+    return 0;
+  const uint32_t n = (r->local_tiles - a.split_tiles) * 16u;
+  if (n == 0) return 0;
+  uint64_t addr = 0;
+  if (ensure(r, (uint64_t)n * sizeof(rt_cdesc_t), &r->cdesc, &addr)) return -1;
+  rt_setup_arg_t g;
+  base_arg(r, &g);
+  g.status_addr = r->su.status.addr;
+  g.order_addr = a.order_addr;
+  g.bidx_addr = a.blist_blocks ? a.bidx_addr : 0;  // no lists in use: every header (0, 0)
+  g.width = a.width;
+  g.height = a.height;
+  g.tiles_x = a.tiles_x;
+  g.tiles_y = a.tiles_y;
+  g.shard_index = a.shard_index;
+  g.shard_count = a.shard_count;
+  g.local_tiles = r->local_tiles;
+  g.cdesc_addr = addr;
+  g.cdesc_n = n;
+  g.cdesc_pos0 = a.split_tiles;
+  g.cdesc_compact = (a.flags & RT_FLAG_COMPACT) ? 1u : 0u;
+  Seq q;
+  q.add(RTS_CDESC);
+  if (run_seq(r, g, q, launches) != 0) return -1;
+  // chunk_map's tiers (rt_trace.h): quad tiles at 64 chunks, the other split
+  // tiles at 1024 >> split_log, then the whole-block tier
+  a.cdesc_first = (a.quad_tiles << 6) + ((a.split_tiles - a.quad_tiles) << (10u - a.split_log));
+  a.cdesc_addr = addr;
+  r->cdesc_n = n;
+  return 0;
+}
+
 int set_light(rt_renderer* r, const float light[3], uint32_t* launches) {
   rt_kernel_arg_t& a = r->arg;
   for (int i = 0; i < 3; ++i) {

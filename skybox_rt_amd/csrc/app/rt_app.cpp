@@ -491,9 +491,26 @@ int rt_renderer_export_records(rt_renderer_h r, uint32_t which, void* out, uint6
       break;
     case RT_REC_SIDX: b = a.slist_on ? r->sidx : nullptr; n = 6ull * a.slist_n * a.slist_n * 8; break;
     case RT_REC_SLIST: b = a.slist_on ? r->slist : nullptr; n = (r->sl_entries + 1) * sizeof(rt_tri_t); break;
+    case RT_REC_CDESC:
+    case RT_REC_CDESC_HOST: b = r->cdesc_n ? r->cdesc : nullptr; n = (uint64_t)r->cdesc_n * sizeof(rt_cdesc_t); break;
     default: return fail("unknown record array");
   }
   if (!b) return fail("record array not present in this configuration");
+  if (which == RT_REC_CDESC_HOST && out) {
+    // the host restatement (app/setup.cpp ChunkDescs) from the device's work order and list headers
+    if (bytes < n) return fail("buffer too small");
+    std::vector<uint32_t> order(a.order_addr ? r->local_tiles : 0u), bidx((size_t)a.blist_blocks * 2);
+    if ((!order.empty() && vx_copy_from_dev(order.data(), r->order, 0, order.size() * 4) != 0) ||
+        (!bidx.empty() && vx_copy_from_dev(bidx.data(), r->bidx, 0, bidx.size() * 4) != 0))
+      return fail("vx_copy_from_dev failed");
+    const std::vector<rt_cdesc_t> d = rt::ChunkDescs(
+        a.width, a.tiles_x, a.shard_index, a.shard_count, (a.flags & RT_FLAG_COMPACT) != 0, a.split_tiles,
+        r->local_tiles, order.empty() ? nullptr : order.data(), bidx.empty() ? nullptr : bidx.data());
+    if (d.size() * sizeof(rt_cdesc_t) != n) return fail("chunk descriptor count mismatch");
+    std::memcpy(out, d.data(), n);
+    if (size) *size = n;
+    return 0;
+  }
   if (size) *size = n;
   if (!out) return 0;
   if (bytes < n) return fail("buffer too small");
@@ -947,6 +964,9 @@ int rt_renderer_configure(rt_renderer_h r, const rt_render_params_t* p) {
                      a.num_geom > 0 && r->local_tiles > 0;
   a.blist_blocks = 0;
   a.blist_addr = a.bidx_addr = 0;
+  a.cdesc_addr = 0;
+  a.cdesc_first = 0;
+  r->cdesc_n = 0;
   r->setup.blist_entries = 0;
   r->setup.blist_max = 0;
   // shadow rays (primary+shadow frames, every path vertex): light-space
@@ -997,6 +1017,12 @@ int rt_renderer_configure(rt_renderer_h r, const rt_render_params_t* p) {
                                               std::min(n, a.quad_tiles) * qextra);
     }
   }
+  // the whole-block tier's chunk descriptors (device setup, the RT images;
+  // env RT_CHUNK_DESC=0: none, the kernels work the task map out themselves)
+  const char* cde = std::getenv("RT_CHUNK_DESC");
+  if (device && !raster && !(p->flags & RT_RENDER_FLAT) && r->local_tiles > 0 && !(cde && std::atoi(cde) == 0) &&
+      rtapp::chunk_desc(r, &launches) != 0)
+    return -1;
   uint64_t args_addr = 0;
   if (r->pq) {
     // the path queue: RT_PQ_SEGS segments (chunk c -> segment c % RT_PQ_SEGS),

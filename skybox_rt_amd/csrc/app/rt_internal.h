@@ -72,6 +72,8 @@ struct rt_renderer {
   vx_buffer_h order = nullptr;
   vx_buffer_h vnodes = nullptr, vtris = nullptr, vlayers = nullptr, vgeom = nullptr;
   vx_buffer_h blist = nullptr, bidx = nullptr;  // per-block candidate lists (rt_bentry_t)
+  vx_buffer_h cdesc = nullptr;   // chunk descriptor table (rt_cdesc_t, device_setup.cpp chunk_desc)
+  uint32_t cdesc_n = 0;          // its records (0: none in this configuration)
   vx_buffer_h sidx = nullptr, slist = nullptr;  // light-space shadow lists (built for sl_light)
   bool sl_mode = false;     // this configuration's shadow rays use the light-space lists
   bool sl_pending = false;  // lists queued by rt_renderer_set_light, status not read yet
@@ -135,7 +137,7 @@ struct rt_renderer {
                            &ptris, &geom, &oms, &bbox, &zbuf, &order, &vnodes, &vtris, &vlayers,
                            &vgeom, &gather_recv, &gather_image, &prims, &cbuf, &args,
                            &setup_krnl, &verts, &pdc, &dcz, &layer_list, &geometry_list, &vis,
-                           &blist, &bidx, &sidx, &slist, &krnl_pq[0][0], &krnl_pq[0][1],
+                           &blist, &bidx, &cdesc, &sidx, &slist, &krnl_pq[0][0], &krnl_pq[0][1],
                            &krnl_pq[1][0], &krnl_pq[1][1], &pathq, &pathq_ctr,
                            &krnl_bvh[0], &krnl_bvh[1], &sah_krnl};
     for (auto* b : bufs) {
@@ -180,6 +182,10 @@ int device_ingest(rt_renderer* r, bool records);
 // slists: the light-space shadow lists for a.light unless current (kept
 // while the light is unchanged; arg.slist_on 0 when they do not fit).  One
 // stream-ordered launch sequence, one status read-back.
+// the chunk descriptor table of the whole-block tier (rt_common.h
+// rt_cdesc_t), one more launch of the setup image behind the configure's
+// sequence; called once the tiers are known, when the block lists are in use
+int chunk_desc(rt_renderer* r, uint32_t* launches);
 int device_setup(rt_renderer* r, bool raster, bool order_on, bool lists, bool slists, uint32_t* heavy,
                  uint32_t* launches);
 // rt_renderer_set_light: the new light into the render arguments and, when

@@ -250,4 +250,25 @@ rt_omstate_t OmState(const DrawCall& dc) {
   return s;
 }
 
+std::vector<rt_cdesc_t> ChunkDescs(uint32_t width, uint32_t tiles_x, uint32_t shard_index,
+                                   uint32_t shard_count, bool compact, uint32_t pos0,
+                                   uint32_t local_tiles, const uint32_t* order, const uint32_t* bidx) {
+  std::vector<rt_cdesc_t> out;
+  for (uint32_t pos = pos0; pos < local_tiles; ++pos) {
+    const uint32_t lt = order ? order[pos] : pos;
+    const uint32_t gt = shard_index + lt * shard_count;
+    const uint32_t tx = gt % tiles_x, ty = gt / tiles_x;
+    for (uint32_t blk = 0; blk < 16; ++blk) {
+      const uint32_t x0 = tx * 32u + (blk & 3u) * 8u, y0 = ty * 32u + (blk >> 2) * 8u;
+      rt_cdesc_t d;
+      d.origin = x0 | (y0 << 16);
+      d.out = compact ? (lt << 10) | ((y0 & 31u) << 5) | (x0 & 31u) : y0 * width + x0;
+      d.first = bidx ? bidx[2 * (lt * 16u + blk)] : 0u;
+      d.count = (bidx ? bidx[2 * (lt * 16u + blk) + 1] : 0u) | ((compact ? 32u : width) << 16);
+      out.push_back(d);
+    }
+  }
+  return out;
+}
+
 }  // namespace rt

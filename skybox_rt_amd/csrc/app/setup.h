@@ -43,4 +43,13 @@ int PrimBBox(const std::array<Vertex, 3>& v, uint32_t width, uint32_t height, rt
 // Output-merger state of a drawcall (raster pipeline).
 rt_omstate_t OmState(const DrawCall& dc);
 
+// The chunk descriptor table of the whole-block tier (rt_common.h
+// rt_cdesc_t; kernels/rt_setup.hip phase_cdesc builds it on the device):
+// record i is work-order position pos0 + i / 16, block i % 16.  `order`
+// (null: identity) and `bidx` (first, count per local block; null: no lists
+// in use, every header (0, 0)) as the setup left them.
+std::vector<rt_cdesc_t> ChunkDescs(uint32_t width, uint32_t tiles_x, uint32_t shard_index,
+                                   uint32_t shard_count, bool compact, uint32_t pos0,
+                                   uint32_t local_tiles, const uint32_t* order, const uint32_t* bidx);
+
 }  // namespace rt

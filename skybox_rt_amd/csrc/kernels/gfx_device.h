@@ -310,6 +310,62 @@ __device__ __forceinline__ uint32_t shade(const vx_arena& A, const Prim& p, cons
                      edge_eval(p.edge(2), x, y));
 }
 
+// Shading specialised on the drawcall's wave-uniform state (RT_SHADE_KEY,
+// rt_trace.h shade_wave): the shading key of a drawcall is its COLOR / TEX /
+// MODULATE flags, filter, the two wraps, format and stride in one word
+// (shade_key); a wave whose drawcall record sits in SGPRs compares the key
+// once and runs an instantiation of shade() with those fields as constants,
+// so the wrap / filter / format / flag selects of the generic code fold away.
+// Same arithmetic in the same order.  The instantiated keys are the most
+// used textured ones of the golden scenes the RT path accepts
+// (tests/test_shade_keys.py lists them from the traces): bilinear, REPEAT /
+// REPEAT, R5G6B5, textured or modulated -- tekkaman's model and backdrop,
+// box.  Every other drawcall runs the generic shade() (untextured ones have
+// no sampler selects to fold; each further key costs the image its text).
+// The key's slots: flags bits 1-3, filter bits 4-7, wrapu 8-11, wrapv 12-15,
+// format 16-23, stride 24-31.  The record's fields are the host setup's
+// (app/setup.cpp DrawcallState): filter 0-1, wraps 0-2, format 0-6 (the
+// VX_TEX_* values below), stride 1, 2 or 4, so no field reaches into a
+// neighbour's slot and two keys are equal only when every field is.
+static_assert(VX_TEX_FILTER_BILINEAR <= 0xf && VX_TEX_WRAP_MIRROR <= 0xf && VX_TEX_FORMAT_A8 <= 0xff &&
+                  (RT_DC_COLOR | RT_DC_TEX | RT_DC_MODULATE) <= 0xf,
+              "shade key slots");
+constexpr uint32_t shade_key_of(uint32_t flags, uint32_t filter, uint32_t wrapu, uint32_t wrapv,
+                                uint32_t format, uint32_t stride) {
+  return (flags & (RT_DC_COLOR | RT_DC_TEX | RT_DC_MODULATE)) | (filter << 4) | (wrapu << 8) |
+         (wrapv << 12) | (format << 16) | (stride << 24);
+}
+__device__ __forceinline__ uint32_t shade_key(const DcState& s) {
+  return shade_key_of(s.flags, s.filter, s.wrapu, s.wrapv, s.format, s.stride);
+}
+template <uint32_t FLAGS, uint32_t FMT, uint32_t STRIDE>
+__device__ __forceinline__ uint32_t shade_as(const vx_arena& A, const Prim& p, const DcState& s,
+                                             uint32_t x, uint32_t y) {
+  DcState k = s;
+  k.flags = FLAGS;
+  k.filter = VX_TEX_FILTER_BILINEAR;
+  k.wrapu = VX_TEX_WRAP_REPEAT;
+  k.wrapv = VX_TEX_WRAP_REPEAT;
+  k.format = FMT;
+  k.stride = STRIDE;
+  return shade(A, p, k, x, y);
+}
+#define GFX_SHADE_KEYS(X)                                                  \
+  X(RT_DC_TEX, VX_TEX_FORMAT_R5G6B5, 2u)                                   \
+  X(RT_DC_TEX | RT_DC_COLOR | RT_DC_MODULATE, VX_TEX_FORMAT_R5G6B5, 2u)
+// `s` wave-uniform (a scalar record): one compare chain per wave
+__device__ __forceinline__ uint32_t shade_keyed(const vx_arena& A, const Prim& p, const DcState& s,
+                                                uint32_t x, uint32_t y) {
+  const uint32_t key = shade_key(s);
+#define GFX_SHADE_CASE(FLAGS, FMT, STRIDE)                                                      \
+  if (key == shade_key_of(FLAGS, VX_TEX_FILTER_BILINEAR, VX_TEX_WRAP_REPEAT, VX_TEX_WRAP_REPEAT, \
+                          FMT, STRIDE))                                                         \
+    return shade_as<(FLAGS), FMT, STRIDE>(A, p, s, x, y);
+  GFX_SHADE_KEYS(GFX_SHADE_CASE)
+#undef GFX_SHADE_CASE
+  return shade(A, p, s, x, y);
+}
+
 // ---- output merger: graphics.cpp:320-636 + gpu_sw.h:100-168 (oracle/gfx.c
 // orc_om_write), for a pixel whose colour and depth/stencil words live in
 // registers of the thread that owns the pixel ----

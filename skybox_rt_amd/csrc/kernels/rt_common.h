@@ -222,7 +222,22 @@ typedef struct {
   uint32_t tiles_x_magic;  // min(ceil(2^32 / tiles_x), 2^32 - 1): a tile's row is
                            // mulhi(tile, magic) plus at most one correction (rt_trace.h
                            // tile_row) -- no integer division in the kernels' task map
+  uint32_t cdesc_first;    // the first chunk of the whole-block tier (the chunks the table covers)
+  uint64_t cdesc_addr;     // rt_cdesc_t per 64-task chunk of the whole-block tier, in work order
+                           // (0: no table, the kernels work the task map out themselves)
 } rt_kernel_arg_t;
+// One 64-task chunk of the whole-block tier (an 8x8 pixel block), written by
+// the device setup (rt_setup.hip RTS_CDESC) and restated on the host
+// (app/setup.cpp ChunkDescs): everything rt_kernel's chunk_map / chunk_pixel
+// and the block's list header give, in one 16-B scalar load.  It depends on
+// the size, the shard, the work order, the buffer layout and the block
+// lists -- not on the light.
+typedef struct {
+  uint32_t origin;  // the block's first pixel: x | y << 16
+  uint32_t out;     // framebuffer word of lane 0 (compact or linear layout resolved)
+  uint32_t first;   // the block's candidate list: first entry in blist
+  uint32_t count;   // its length (bits 0-15) | the framebuffer words per pixel row << 16
+} rt_cdesc_t;
 // the reciprocal rt_kernel_arg_t::tiles_x_magic holds for `tiles_x` tiles per row
 static inline uint32_t rt_tiles_x_magic(uint32_t tiles_x) {
   if (tiles_x <= 1) return 0xffffffffu;

@@ -86,10 +86,35 @@ __device__ __forceinline__ void kernel_body(const vx_task_t& task, const Scene& 
                                             Counters& cnt) {
   const uint32_t t = task.blockIdx.x;
   // the chunk's task map in scalar registers (every lane runs the same chunk)
-  const ChunkMap cm = chunk_map(S, task_args(S), (uint32_t)__builtin_amdgcn_readfirstlane(t) >> 6);
+  const uint32_t c = (uint32_t)__builtin_amdgcn_readfirstlane(t) >> 6;
   uint32_t x, y, out;
+#if RT_CHUNK_DESC && !RT_BVH_WALK
+  // a chunk of the whole-block tier with the setup's descriptor table: the
+  // block's origin, lane 0's framebuffer word and the list header in one
+  // scalar load; other tiers, or no table: chunk_map and the bidx load
+  uint2 oc = make_uint2(0u, 0u);
+  if (S.cdesc != 0 && c >= S.cdesc_first) {
+    const uint4 d = S.A.sld_u4(S.cdesc + 16u * (c - S.cdesc_first));
+    uint32_t ln = t & 63u;
+    asm volatile("" : "+v"(ln));  // worked out here: hoisted out of the chunk loop its parts spill
+    x = (d.x & 0xffffu) + (ln & 7u);
+    y = (d.x >> 16) + (ln >> 3);
+    out = d.y + (ln >> 3) * (d.w >> 16) + (ln & 7u);
+    oc = make_uint2(d.z, d.w & 0xffffu);
+  } else {
+    const ChunkMap cm = chunk_map(S, task_args(S), c);
+    uint32_t cx, cy, co;
+    chunk_pixel(S, cm, t & 63u, &cx, &cy, &co);
+    x = cx;
+    y = cy;
+    out = co;
+    if (S.blist_blocks) oc = block_header(S, (cm.lt << 4) | cm.blk);
+  }
+#else
+  const ChunkMap cm = chunk_map(S, task_args(S), c);
   chunk_pixel(S, cm, t & 63u, &x, &y, &out);
   const uint32_t lb = (cm.lt << 4) | cm.blk;
+#endif
   const bool in = x < S.width && y < S.height;  // edge tiles overhang the image
   cnt.primary += in;
   const bool tie_high = (S.flags & RT_FLAG_TIE_HIGH) != 0;
@@ -97,7 +122,17 @@ __device__ __forceinline__ void kernel_body(const vx_task_t& task, const Scene& 
   if (lane_id() == 0) __vx_mpm_lds[3] = (uint32_t)__builtin_amdgcn_s_memrealtime();
 #endif
   // primary visibility: the raster's winner at this pixel
+#if RT_CHUNK_DESC && !RT_BVH_WALK
+  int32_t hit;
+  if (S.blist_blocks) {
+    hit = block_primary(S, oc, x, y, in, tie_high, cnt);
+  } else {  // no lists: the packet walk of the tree (trace_primary)
+    const int32_t h = trace_primary_packet(walk_scene(S), x, y, in, tie_high, cnt);
+    hit = in ? h : -1;
+  }
+#else
   const int32_t hit = trace_primary(S, lb, x, y, in, tie_high, cnt);
+#endif
 #ifdef RT_STAMPS
   if (lane_id() == 0) __vx_mpm_lds[14] = (uint32_t)__builtin_amdgcn_s_memrealtime();
 #endif
@@ -122,7 +157,7 @@ __device__ __forceinline__ void kernel_body(const vx_task_t& task, const Scene& 
   (void)w;
   return;
 #endif
-  const bool shadow = hit >= 0 && secondary_ok(th) && (S.flags & RT_FLAG_SHADOWS) != 0;
+  const bool shadow = hit >= 0 && secondary_ok(th) && (rt_usgpr(S.flags) & RT_FLAG_SHADOWS) != 0;
   // wave64 compaction: lanes with a pending shadow ray append it to the
   // wave's LDS queue at ballot/mbcnt-assigned slots
   const uint64_t m = __ballot(shadow);
@@ -160,7 +195,7 @@ __device__ __forceinline__ void shadow_drain(bool final, const Scene& S, WaveLds
   if (!final && w.q_count >= 64 && lane_id() == 0)
     __vx_mpm_lds[6] = (uint32_t)__builtin_amdgcn_s_memrealtime();
 #endif
-  if (!(S.flags & RT_FLAG_SHADOWS)) return;
+  if (!(rt_usgpr(S.flags) & RT_FLAG_SHADOWS)) return;
   const uint32_t lane = lane_id();
   uint32_t n = w.q_count;
   const bool tie_high = (S.flags & RT_FLAG_TIE_HIGH) != 0;
@@ -178,10 +213,10 @@ __device__ __forceinline__ void shadow_drain(bool final, const Scene& S, WaveLds
     float ts;
     // the light-space lists when built (occluded_list), else the BVH: the
     // binary16 BVH4 as one packet, other layouts per lane (deep images)
-    const bool occ = !RT_BVH_WALK && S.slist_on ? occluded_list(S, s, active, w.q_pid[slot], cnt)
+    const bool occ = !RT_BVH_WALK && rt_usgpr(S.slist_on) ? occluded_list(S, s, active, w.q_pid[slot], cnt)
                      : (RT_ONLY_BVH4H || (S.flags & RT_FLAG_BVH4H))
-                         ? occluded_packet(S, s, active, w.q_pid[slot], 1.0f, cnt)
-                         : active && trace<true>(S, s, 0.0f, 1.0f, w.q_pid[slot], tie_high, &ts,
+                         ? occluded_packet(walk_scene(S), s, active, w.q_pid[slot], 1.0f, cnt)
+                         : active && trace<true>(walk_scene(S), s, 0.0f, 1.0f, w.q_pid[slot], tie_high, &ts,
                                                  RT_WSTACK(w, lane), cnt) >= 0;
     if (occ) {
       ++cnt.occluded;

@@ -1248,6 +1248,33 @@ __device__ void phase_records(const rt_setup_arg_t* a) {
   }
 }
 
+// The chunk descriptor table (rt_common.h rt_cdesc_t): record i is the
+// whole-block tier's chunk i -- work-order position cdesc_pos0 + i / 16, 8x8
+// block i % 16 of that tile -- with what rt_trace.h chunk_map / chunk_pixel
+// and the block's list header give (app/setup.cpp ChunkDescs restates it).
+// Runs in a launch after the order's SCATTER and the lists' BOFF.
+__device__ void phase_cdesc(const rt_setup_arg_t* a) {
+  const uint32_t* order = a->order_addr ? vx_ptr<const uint32_t>(a->order_addr) : nullptr;
+  const uint2* bidx = a->bidx_addr ? vx_ptr<const uint2>(a->bidx_addr) : nullptr;  // null: no lists in use
+  rt_cdesc_t* out = vx_ptr<rt_cdesc_t>(a->cdesc_addr);
+  for (uint32_t i = slice_b() * RTS_BLOCK + threadIdx.x; i < a->cdesc_n; i += slice_n() * RTS_BLOCK) {
+    const uint32_t pos = a->cdesc_pos0 + (i >> 4), blk = i & 15u;
+    if (pos >= a->local_tiles) continue;
+    const uint32_t lt = order ? order[pos] : pos;
+    if (lt >= a->local_tiles) continue;  // (a malformed order: the record stays unwritten)
+    const uint32_t gt = a->shard_index + lt * a->shard_count;
+    const uint32_t ty = gt / a->tiles_x, tx = gt - ty * a->tiles_x;
+    const uint32_t x0 = (tx << RT_TILE_LOG) + ((blk & 3u) << 3), y0 = (ty << RT_TILE_LOG) + ((blk >> 2) << 3);
+    const uint2 oc = bidx ? bidx[(lt << 4) | blk] : make_uint2(0u, 0u);
+    rt_cdesc_t d;
+    d.origin = x0 | (y0 << 16);
+    d.out = a->cdesc_compact ? (lt << 10) | ((y0 & 31u) << 5) | (x0 & 31u) : y0 * a->width + x0;
+    d.first = oc.x;
+    d.count = oc.y | ((a->cdesc_compact ? 32u : a->width) << 16);
+    out[i] = d;
+  }
+}
+
 // one wide sub-phase (on this workgroup's slice, slice_b() / slice_n())
 __device__ void run_phase(const rt_setup_arg_t* arg, uint32_t bit) {
   switch (bit) {
@@ -1273,17 +1300,19 @@ __device__ void run_phase(const rt_setup_arg_t* arg, uint32_t bit) {
     case RTS_SOFF: phase_loff(cell_set(arg), (arg->fold & RTS_FOLD_LISTS) != 0); break;
     case RTS_SFILL: phase_sfill(arg); break;
     case RTS_SSORT: phase_ssort(arg); break;
+    case RTS_CDESC: phase_cdesc(arg); break;
     default: break;
   }
 }
 // the wide sub-phases in run order, with their shares of a partitioned
 // launch's workgroups (the per-primitive scan of PRIMVIS and the per-entry
 // list phases carry the longest per-workgroup chains)
-__constant__ const uint32_t kWide[22][2] = {
+__constant__ const uint32_t kWide[23][2] = {
     {RTS_FILL, 2},   {RTS_PRIMVIS, 16}, {RTS_SPROJ, 3},  {RTS_VTRIS, 1},  {RTS_WEIGHT, 1},  {RTS_LINK, 3},
     {RTS_ROWSUM, 1}, {RTS_CLIMB, 3},   {RTS_COLSUM, 1}, {RTS_HIST, 1},   {RTS_SCATTER, 2}, {RTS_RECORDS, 2},
     {RTS_BCOUNT, 2}, {RTS_BSUM, 1},    {RTS_BOFF, 1},   {RTS_BFILL, 2},  {RTS_BSORT, 4},   {RTS_SCOUNT, 3},
-    {RTS_SSUM, 1},   {RTS_SOFF, 2},    {RTS_SFILL, 3},  {RTS_SSORT, 3}};
+    {RTS_SSUM, 1},   {RTS_SOFF, 2},    {RTS_SFILL, 3},  {RTS_SSORT, 3},
+    {RTS_CDESC, 1}};
 // the wide sub-phases of `ph` (each independent of the others in the same
 // launch).  part: each on its own slice of the grid, in proportion to its
 // share, so they run side by side (a launch then takes about its longest
@@ -1291,11 +1320,11 @@ __constant__ const uint32_t kWide[22][2] = {
 __device__ void run_phases(const rt_setup_arg_t* arg, uint32_t ph, bool part) {
   if ((ph & RTS_CLIMB) && arg->num_nodes <= RTS_CLIMB_WG_NODES) ph &= ~RTS_CLIMB;  // one workgroup: run_scans
   uint32_t total = 0;
-  for (int i = 0; i < 22; ++i) total += (ph & kWide[i][0]) ? kWide[i][1] : 0u;
+  for (int i = 0; i < 23; ++i) total += (ph & kWide[i][0]) ? kWide[i][1] : 0u;
   if (total == 0) return;
   const uint32_t G = gridDim.x;
   uint32_t cum = 0;
-  for (int i = 0; i < 22; ++i) {
+  for (int i = 0; i < 23; ++i) {
     const uint32_t bit = kWide[i][0];
     if (!(ph & bit)) continue;
     uint32_t b0 = 0, b1 = G;

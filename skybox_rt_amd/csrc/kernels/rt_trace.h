@@ -32,6 +32,32 @@
 #ifndef RT_BVH_WALK
 #define RT_BVH_WALK 0  // 1: image rt_bvh -- primary and shadow rays walk the BVH, no list code
 #endif
+// the scalar-stream knobs (profiles/r07/ab keeps the
+// all-on / leave-one-out record):
+//   RT_SHADE_KEY   shade_wave branches once per wave-uniform drawcall to a
+//                  shade() instantiated on its key (gfx_device.h shade_keyed)
+//   RT_LEAN_SCENE  the packet-walk fallbacks' node arrays are read from the
+//                  argument block where used, not at wave start
+//   RT_UTEST       wave-uniform flag tests (compact, shadows, lists on) are
+//                  made where used from the flag word in its SGPR (a scalar
+//                  compare and branch) instead of being hoisted to the wave's
+//                  start as 64-bit lane masks that then spill
+#ifndef RT_SHADE_KEY
+#define RT_SHADE_KEY 0
+#endif
+#ifndef RT_LEAN_SCENE
+#define RT_LEAN_SCENE 0
+#endif
+//   RT_CHUNK_DESC  a chunk of the whole-block tier reads its pixel origin,
+//                  framebuffer word and block-list header from the setup's
+//                  descriptor table (rt_common.h rt_cdesc_t): one 16-B scalar
+//                  load in place of chunk_map and the bidx load
+#ifndef RT_UTEST
+#define RT_UTEST 0
+#endif
+#ifndef RT_CHUNK_DESC
+#define RT_CHUNK_DESC 0
+#endif
 
 namespace rtk {
 
@@ -51,6 +77,15 @@ struct Counters {
 #endif
 };
 
+// A wave-uniform word as it stands in its SGPR at this point (RT_UTEST): the
+// test on it is made here, not hoisted and kept as a lane mask.
+__device__ __forceinline__ uint32_t rt_usgpr(uint32_t v) {
+#if RT_UTEST
+  asm volatile("" : "+s"(v));
+#endif
+  return v;
+}
+
 // Kernel arguments in scalar registers; buffer addresses become 32-bit
 // arena offsets (rt_app checks every buffer lies below 4 GiB).
 struct Scene {
@@ -64,7 +99,11 @@ struct Scene {
   uint64_t argp;  // the argument block (constant address space), for lazy_args
   uint32_t blist, bidx, blist_blocks;  // per-block candidate lists (rt_bentry_t)
   uint32_t sidx, slist, slist_on, slist_n;  // light-space shadow lists (rt_common.h)
+  uint32_t cdesc, cdesc_first;  // chunk descriptor table (RT_CHUNK_DESC; cdesc 0: none)
 };
+// sizeof(Scene) past the arena descriptor: walk_scene() copies the fields one
+// by one and asserts this size, so a new field cannot be left out unnoticed
+#define RT_SCENE_TAIL_BYTES 192
 
 // The argument block is read through the scalar cache (constant address
 // space, wave-uniform address): the scene's fields then live in SGPRs, and
@@ -84,14 +123,19 @@ __device__ __forceinline__ Scene load_scene(const rt_kernel_arg_t* ga, const vx_
   Scene s;
   s.argp = (uint64_t)a;
   s.A = vx_arena::get();
+#if RT_LEAN_SCENE
+  // the packet walks' arrays: walk_scene(), where a walk starts
+  s.nodes = s.nodes4 = s.tris = s.vnodes = s.vtris = s.num_vnodes = 0;
+#else
   s.nodes = (uint32_t)a->nodes_addr;
   s.nodes4 = (uint32_t)a->nodes4_addr;
   s.tris = (uint32_t)a->tris_addr;
   s.vnodes = (uint32_t)a->vnodes_addr;
   s.vtris = (uint32_t)a->vtris_addr;
+  s.num_vnodes = a->num_vnodes;
+#endif
   s.vlayers = (uint32_t)a->vlayers_addr;
   s.vgeom = (uint32_t)a->vgeom_addr;
-  s.num_vnodes = a->num_vnodes;
   s.prims = (uint32_t)a->prims_addr;
   s.dcs = (uint32_t)a->dcs_addr;
   s.cbuf = (uint32_t)a->cbuf_addr;
@@ -133,7 +177,53 @@ __device__ __forceinline__ Scene load_scene(const rt_kernel_arg_t* ga, const vx_
     s.light[2] = __builtin_bit_cast(float, lw.w[2]);
   }
   if (lw.w[3] & RT_LW_NO_SLIST) s.slist_on = 0;
+#if RT_CHUNK_DESC
+  s.cdesc = (uint32_t)a->cdesc_addr;
+  s.cdesc_first = a->cdesc_first;
+#else
+  s.cdesc = s.cdesc_first = 0;
+#endif
   return s;
+}
+
+// The scene as the BVH walks read it: with RT_LEAN_SCENE the node / triangle
+// arrays of the walks (the list images' fallbacks: no block lists, stale
+// shadow lists) are read here, through an opaque pointer as task_args does,
+// instead of by every wave at its start.
+__device__ __forceinline__ Scene walk_scene(const Scene& S) {
+#if RT_LEAN_SCENE
+  // (field by field: a whole-struct copy leaves light[] a stack object; a
+  // field added to Scene goes into this list too -- the size below then
+  // changes and says so)
+  static_assert(sizeof(Scene) == sizeof(vx_arena) + RT_SCENE_TAIL_BYTES,
+                "Scene changed: add the new field to walk_scene's copy list and update RT_SCENE_TAIL_BYTES");
+  Scene w;
+  w.A = S.A;
+#define RT_COPY(f) w.f = S.f;
+  RT_COPY(prims) RT_COPY(dcs) RT_COPY(cbuf) RT_COPY(ptris) RT_COPY(geom) RT_COPY(order)
+  RT_COPY(vlayers) RT_COPY(vgeom) RT_COPY(num_nodes) RT_COPY(num_nodes4) RT_COPY(num_layer)
+  RT_COPY(num_geom) RT_COPY(flags) RT_COPY(width) RT_COPY(height) RT_COPY(shard_index)
+  RT_COPY(shard_count) RT_COPY(tiles_x) RT_COPY(clear_color) RT_COPY(bounces) RT_COPY(seed)
+  RT_COPY(split_tiles) RT_COPY(split_log) RT_COPY(tiles_x_magic) RT_COPY(num_tasks) RT_COPY(argp) RT_COPY(blist)
+  RT_COPY(bidx) RT_COPY(blist_blocks) RT_COPY(sidx) RT_COPY(slist) RT_COPY(slist_on) RT_COPY(slist_n)
+  RT_COPY(cdesc) RT_COPY(cdesc_first)
+#undef RT_COPY
+  // (the walks shoot no ray of their own: primary_dir / shadow_ray's fields stay out of the copy)
+  w.sx = w.sy = w.light[0] = w.light[1] = w.light[2] = 0.0f;
+  uint64_t p = S.argp;
+  asm volatile("" : "+s"(p));
+  const __attribute__((address_space(4))) rt_kernel_arg_t* a =
+      (const __attribute__((address_space(4))) rt_kernel_arg_t*)p;
+  w.nodes = (uint32_t)a->nodes_addr;
+  w.nodes4 = (uint32_t)a->nodes4_addr;
+  w.tris = (uint32_t)a->tris_addr;
+  w.vnodes = (uint32_t)a->vnodes_addr;
+  w.vtris = (uint32_t)a->vtris_addr;
+  w.num_vnodes = a->num_vnodes;
+  return w;
+#else
+  return S;
+#endif
 }
 
 __device__ __forceinline__ uint32_t lane_id() {
@@ -1151,6 +1241,12 @@ __device__ __forceinline__ uint32_t shade_lane(const Scene& S, int32_t pid, uint
 // bytes in every lane); other waves per lane.  Same records, same
 // arithmetic.  Config 3 A/B (r03r, with the counter gate of vx_spawn.h):
 // 0.02256 -> 0.01982 ms.
+// (RT_SHADE: the shade of a wave-uniform drawcall record, RT_SHADE_KEY)
+#if RT_SHADE_KEY
+#define RT_SHADE gfx::shade_keyed
+#else
+#define RT_SHADE gfx::shade
+#endif
 __device__ __forceinline__ uint32_t shade_wave(const Scene& S, int32_t spid, uint32_t x,
                                                uint32_t y, uint32_t color, Counters& cnt) {
   const uint64_t need = __ballot(spid >= 0);
@@ -1166,7 +1262,7 @@ __device__ __forceinline__ uint32_t shade_wave(const Scene& S, int32_t spid, uin
       ++cnt.shaded;
       if (s.flags & RT_DC_TEX) cnt.texel_bytes += (s.filter == VX_TEX_FILTER_BILINEAR ? 4u : 1u) * s.stride;
 #endif
-      color = gfx::shade(S.A, p, s, x, y);
+      color = RT_SHADE(S.A, p, s, x, y);
     }
     return color;
   }
@@ -1189,7 +1285,7 @@ __device__ __forceinline__ uint32_t shade_wave(const Scene& S, int32_t spid, uin
       ++cnt.shaded;
       if (s.flags & RT_DC_TEX) cnt.texel_bytes += (s.filter == VX_TEX_FILTER_BILINEAR ? 4u : 1u) * s.stride;
 #endif
-      color = gfx::shade(S.A, p, s, x, y);
+      color = RT_SHADE(S.A, p, s, x, y);
     }
   }
   return color;
@@ -1387,12 +1483,16 @@ __device__ __forceinline__ int32_t trace_primary_packet(const Scene& S, uint32_t
 // count once per wave per record tested, as the packet walk's do.  Every
 // lane of the wave calls it with the wave's local block `lb` (uniform);
 // lanes with !act get -1.
-__device__ __forceinline__ int32_t block_primary(const Scene& S, uint32_t lb, uint32_t px, uint32_t py,
+// (`oc`: the block's list header -- first entry, count -- from bidx or
+// from the chunk's descriptor)
+__device__ __forceinline__ uint2 block_header(const Scene& S, uint32_t lb) {
+  return S.A.sld<uint2>(S.bidx + 8u * lb);
+}
+__device__ __forceinline__ int32_t block_primary(const Scene& S, uint2 oc, uint32_t px, uint32_t py,
                                                  bool act, bool tie_high, Counters& cnt) {
   (void)cnt;
   if (!act) px = 0xffffffffu;
   const uint32_t pp = px > 0xffffu ? 0xffffffffu : px | (py << 16);
-  const uint2 oc = S.A.sld<uint2>(S.bidx + 8u * lb);
   uint32_t bz = VX_OM_DEPTH_MASK;
   int32_t bpid = -1;
   // (skipping the list load of a block no candidate reaches measured no
@@ -1420,8 +1520,9 @@ __device__ __forceinline__ int32_t block_primary(const Scene& S, uint32_t lb, ui
 // the host built lists (blist_blocks), else the packet walk of the tree
 __device__ __forceinline__ int32_t trace_primary(const Scene& S, uint32_t lb, uint32_t px, uint32_t py,
                                                  bool act, bool tie_high, Counters& cnt) {
-  if (!RT_BVH_WALK && S.blist_blocks) return block_primary(S, lb, px, py, act, tie_high, cnt);
-  const int32_t h = trace_primary_packet(S, px, py, act, tie_high, cnt);
+  if (!RT_BVH_WALK && rt_usgpr(S.blist_blocks))
+    return block_primary(S, block_header(S, lb), px, py, act, tie_high, cnt);
+  const int32_t h = trace_primary_packet(walk_scene(S), px, py, act, tie_high, cnt);
   return act ? h : -1;
 }
 
@@ -1653,7 +1754,7 @@ __device__ __forceinline__ void chunk_pixel(const Scene& S, const ChunkMap& m, u
   *x = live ? px : 0xffffffffu;
   *y = (m.ty << RT_TILE_LOG) + ((m.blk >> 2) << 3) + (ib >> 3);
   // compact shard buffers: local-tile order, each tile row-major (store_pixel)
-  *out = (S.flags & RT_FLAG_COMPACT) ? (m.lt << 10) | ((*y & 31u) << 5) | (px & 31u) : *y * S.width + px;
+  *out = (rt_usgpr(S.flags) & RT_FLAG_COMPACT) ? (m.lt << 10) | ((*y & 31u) << 5) | (px & 31u) : *y * S.width + px;
 }
 __device__ __forceinline__ void store_out(const Scene& S, uint32_t out, uint32_t color) {
   S.A.st_u32(S.cbuf + 4u * out, color);

@@ -71,6 +71,7 @@
 #define RTS_SSUM     0x800000u // BSUM over the cells
 #define RTS_SSCAN    0x1000000u // BSCAN over the cells
 #define RTS_SOFF     0x2000000u // BOFF over the cells -> sidx
+#define RTS_CDESC    0x4000000u // thread per whole-block chunk: rt_cdesc_t (rt_common.h) from order + bidx
 
 // status words (u32 [RTS_STATUS_WORDS]): [0] malformed-input flags
 // (RTS_ERR_*), [1] the longest block list, [2] block-list entries in total,
@@ -162,5 +163,9 @@ typedef struct {
   // RTS_FOLD_*: the scans done inside the launches that need them (each
   // workgroup scans what it reads; no one-workgroup scan launch)
   uint32_t fold;
-
+  // RTS_CDESC: the chunk descriptor table of the whole-block tier
+  uint32_t cdesc_n;        // records: (local_tiles - cdesc_pos0) * 16
+  uint64_t cdesc_addr;     // rt_cdesc_t [cdesc_n]
+  uint32_t cdesc_pos0;     // the tier's first position in the work order (= the split tiles)
+  uint32_t cdesc_compact;  // the framebuffer is the compact shard layout (RT_FLAG_COMPACT)
 } rt_setup_arg_t;

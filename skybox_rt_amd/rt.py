@@ -35,6 +35,7 @@ RECORDS = {"prims": (0, np.int32, 32), "bbox": (1, np.uint32, 2), "vis": (2, np.
            "vnodes": (3, np.uint32, 16), "vtris": (4, np.int32, 16), "vlayers": (5, np.int32, 16),
            "vgeom": (6, np.int32, 16), "order": (7, np.uint32, 1), "ptris": (8, np.float32, 12),
            "geom": (9, np.float32, 12), "bidx": (10, np.uint32, 2), "blist": (11, np.uint32, 4),
+           "cdesc": (14, np.uint32, 4), "cdesc_host": (15, np.uint32, 4),
            "sidx": (12, np.uint32, 2), "slist": (13, np.float32, 12)}
 RT_BVH_STACK4_UNUSED = 0xFFFFFFFF
 RT_BVH_BUILD_HOST = 2
