@@ -97,6 +97,24 @@ typedef int (*vx_hip_timing_source_t)(vx_device_h hdevice, int* last_stamped, ui
  * that reach the kernel with its dispatch packet instead of through a copy
  * queued between two launches */
 typedef int (*vx_hip_set_launch_words_t)(vx_device_h hdevice, const uint32_t* words, uint32_t n);
+/* the launch lane (0 or 1) of the next vx_start (then none again).  The
+ * driver runs two streams: lane 0, its own stream, where every launch without
+ * a lane, every copy, every launch of a group and a launch on an idle queue
+ * that its completion kernel follows run in issue order (ordinary
+ * operations), and lane 1.  Any other launch with a lane is ordered only
+ * behind the earlier launches of its lane and
+ * behind every ordinary operation issued before it -- not behind the other
+ * lane's launches, so two launches on lanes 0 and 1 may run on the device at
+ * the same time (a launch with counter rows on -- vx_hip_set_counters, env
+ * VX_HIP_COUNTERS, VORTEX_PROFILING -- stays an ordinary one: the rows of two
+ * launches in flight would mix); the caller keeps what they write apart (the RT app: two
+ * framebuffers, frame parity = lane).  An ordinary operation runs behind the
+ * launches of both lanes.  vx_ready_wait and every call that waits for the
+ * device wait for both lanes.  lane -1 withdraws the request.  Env
+ * VX_HIP_OVERLAP=0 (read at device open): one lane, every launch is an
+ * ordinary one and this call returns -1 for any lane -- how a caller learns
+ * (with lane -1) whether launches can overlap before it sets up for them. */
+typedef int (*vx_hip_set_launch_lane_t)(vx_device_h hdevice, int lane);
 
 #ifdef __cplusplus
 }

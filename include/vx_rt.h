@@ -127,6 +127,22 @@ int rt_scene_vis_tree(rt_scene_h scene, uint32_t width, uint32_t height, float d
 int rt_renderer_create(rt_scene_h scene, const char* kernel_dir, rt_renderer_h* out);
 int rt_renderer_free(rt_renderer_h r);
 int rt_renderer_configure(rt_renderer_h r, const rt_render_params_t* params);
+/* Start a frame without waiting for it.  Frames started back to back queue
+ * on the device (the driver's VX_HIP_QUEUE_DEPTH).  A configuration whose
+ * frame is one launch that writes only framebuffer pixels -- whole
+ * (not compact / sharded) primary+shadow, flat or one-kernel path frames
+ * without counters -- keeps two framebuffers: frame n renders into buffer
+ * n mod 2 on the driver's launch lane n mod 2 (vortex_hip.h
+ * vx_hip_set_launch_lane), so two consecutive frames may run on the device
+ * at the same time (the first waves of one fill the slots the last waves of
+ * the other leave empty) while frames sharing a buffer stay ordered.  Every
+ * other frame, and everything that is not a frame (setup launches, list
+ * rebuilds, uploads), runs behind the frames in flight on both lanes and
+ * ahead of every frame started after it; so does the frame right behind a
+ * list rebuild.  rt_render (start + wait) is such
+ * an ordinary frame too: it renders into the buffer in use, the synchronous
+ * path of the rounds before.  Env VX_HIP_OVERLAP=0: one lane, one
+ * framebuffer, the frames run one after the other. */
 int rt_render_start(rt_renderer_h r);
 int rt_render_wait(rt_renderer_h r);
 int rt_render(rt_renderer_h r);  /* start + wait */
@@ -146,8 +162,12 @@ int rt_render_run_totals(rt_renderer_h r, double* kernel_ms_sum, uint64_t* timed
  * Waits for the in-flight frames. */
 int rt_render_set_timing(rt_renderer_h r, int timed);
 /* linear W*H framebuffer (shard_count == 1) or compact tile buffer
- * (local_tiles * 1024 pixels in task order) */
+ * (local_tiles * 1024 pixels in task order) of the last started frame */
 int rt_read_framebuffer(rt_renderer_h r, uint32_t* out, uint64_t count);
+/* the frame started before it, while the configuration keeps two
+ * framebuffers (rt_render_start) and two frames were started since the
+ * configure; an error otherwise */
+int rt_read_framebuffer_prev(rt_renderer_h r, uint32_t* out, uint64_t count);
 
 /* RT_RENDER_RASTER: the depth/stencil buffer (stencil << 24 | depth), W*H */
 int rt_read_depthbuffer(rt_renderer_h r, uint32_t* out, uint64_t count);
@@ -241,7 +261,10 @@ int rt_renderer_setup_stats(rt_renderer_h r, rt_setup_stats_t* stats);
  * the frames already started, with no host wait; the frames started after it
  * see the new light.  When the configuration's shadow rays use the
  * light-space lists, the lists for the new light are a stream-ordered chain
- * of setup launches (kernels/rt_setup.hip SPROJ .. SSORT, ~0.1 ms at 1024^2)
+ * of setup launches (kernels/rt_setup.hip SPROJ .. SSORT, ~0.1 ms at 1024^2;
+ * with overlapped frames the chain waits for the frames in flight on both
+ * launch lanes before it overwrites the lists, and the frames started after
+ * it wait for it on either lane)
  * whose last launch decides on the device whether they fit (else the frames'
  * shadow rays walk the BVH).  By default (rt_renderer_set_list_policy) the
  * chain is deferred: the frames after the change trace their shadow rays by
@@ -294,7 +317,10 @@ struct rt_shard_comm;
 int rt_render_gather(rt_renderer_h r, struct rt_shard_comm* comm, uint32_t* image);
 
 /* device pointer + byte size of the output buffer (for RCCL gathers) and the
- * HIP stream the kernel runs on (for stream-ordered consumers) */
+ * HIP stream the kernel runs on (for stream-ordered consumers).  The pointer
+ * names the last started frame's buffer; from this call to the next
+ * configure every frame renders into that one buffer on lane 0, the stream
+ * rt_device_stream returns (no frame overlap, rt_render_start). */
 int rt_framebuffer_device(rt_renderer_h r, void** device_ptr, uint64_t* bytes);
 int rt_device_stream(rt_renderer_h r, void** hip_stream);
 int rt_device_caps(rt_renderer_h r, uint64_t caps[8]);

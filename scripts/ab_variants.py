@@ -2,13 +2,16 @@
 """Interleaved A/B timing of kernel-image variants in one process on one GPU
 (cdna_hip_programming.md section 5.4 rule 24): per round each variant's
 back-to-back frames (the bench's kernel clock: events on the driver's stream
-around `frames` launches with per-launch timing off) and three synchronous
+around `frames` launches, at least 200, with per-launch timing off: the frame
+period on the device) and three synchronous
 frames' device times.
 
 A variant is `label=dir[:ENV=VAL[:ENV=VAL...]]`, where `dir` is `default`
 (skybox_rt_amd/lib) or a directory name under skybox_rt_amd/lib/variants and
 the ENV settings are applied while that variant's device is opened (e.g.
-VX_HIP_BLOCKS_PER_CU).  A bare name means `name=name`.  Every variant must
+VX_HIP_BLOCKS_PER_CU; `on=default:VX_HIP_OVERLAP=1,off=default:VX_HIP_OVERLAP=0`
+compares overlapped and ordered frames of the same build).  A bare name means
+`name=name`.  Every variant must
 render the identical framebuffer (checked against the first); prints median /
 min kernel ms per variant as one JSON line."""
 import argparse
@@ -88,7 +91,11 @@ def main():
             r = rs[n]
             # back-to-back frames (no per-launch events, the bench's kernel
             # clock): two events on the driver's stream around them / frames
-            times[n].append(back_to_back_ms(r, max(args.frames, 20)))
+            # (at least 200: with frames overlapped on the driver's two launch
+            # lanes the last frame may run on lane 1 and end after the closing
+            # event on lane 0 -- one frame's overlap in the whole run while the
+            # lanes advance in step, which the traces show but nothing enforces)
+            times[n].append(back_to_back_ms(r, max(args.frames, 200)))
             for _ in range(3):  # and a synchronous frame's device time (completion stamps)
                 r.render()
                 sync[n].append(r.kernel_ms())

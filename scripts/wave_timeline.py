@@ -63,6 +63,13 @@ def main():
         "sum_wave_us_over_span": round(float(dur.sum()) / float(span), 1),
         "last_start_to_end_us": round(float(span - t0.max()) / 100, 1),
     }
+    # the frame boundary: from the frame's start to 90 % of the peak resident
+    # waves, and from the last 1-us bucket at 90 % to the frame's end -- the
+    # parts of a frame another frame's waves could fill
+    full = np.nonzero(alive >= 0.9 * alive.max())[0]
+    out["peak_alive"] = int(alive.max())
+    out["ramp_to_90pct_us"] = float(full[0])
+    out["drain_from_90pct_us"] = round(float(span) / 100.0 - float(full[-1] + 1), 1)
     slow = np.argsort(dur)[-50:]
     out["slowest50"] = {"wave_us": float(dur[slow].mean()) / 100,
                         "primary_us": float(prim[slow].mean()) / 100,

@@ -557,6 +557,7 @@ int set_light(rt_renderer* r, const float light[3], uint32_t* launches) {
 int queue_lists(rt_renderer* r, uint32_t* launches) {
   rt_kernel_arg_t& a = r->arg;
   r->sl_stale = false;
+  r->lane_break = true;  // the frame behind these launches is an ordinary one (rt_internal.h)
   // the shadow lists for the current light, queued behind it: the chain's last
   // launch writes the render arguments' slist_on (the lists' own verdict),
   // so no host wait anywhere; the status words are read when asked for

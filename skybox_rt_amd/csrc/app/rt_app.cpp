@@ -298,6 +298,7 @@ int rt_renderer_create(rt_scene_h s, const char* kernel_dir, rt_renderer_h* out)
   if (const char* e = std::getenv("RT_SLIST_DEFER")) r->sl_defer = (uint32_t)std::atoi(e);
   r->set_tag = (vx_hip_set_launch_tag_t)vx_driver_symbol("vx_hip_set_launch_tag");
   r->set_words = (vx_hip_set_launch_words_t)vx_driver_symbol("vx_hip_set_launch_words");
+  r->set_lane = (vx_hip_set_launch_lane_t)vx_driver_symbol("vx_hip_set_launch_lane");
   r->host_mem = (vx_hip_host_mem_t)vx_driver_symbol("vx_hip_host_mem");
   if (r->host_mem) {
     void* h = nullptr;
@@ -1046,6 +1047,30 @@ int rt_renderer_configure(rt_renderer_h r, const rt_render_params_t* p) {
   } else {
     a.pathq_addr = a.pathq_ctr_addr = 0;
   }
+  // Frame overlap: a configuration whose frame is one launch writing only
+  // framebuffer pixels (and the same task count every frame) gets a second
+  // framebuffer, and its frames alternate between the two buffers and the
+  // driver's two launch lanes (rt_render_start).  Not with counters (the
+  // counter rows of two frames would mix), not compact / sharded (the gather
+  // copies from the one pointer rt_framebuffer_device gave it), not the
+  // two-kernel path tracer, not the raster pipeline (depth buffer, blending),
+  // not the RT_TILE_LIMIT probe (its frames leave pixels unwritten).
+  r->lanes = false;
+  r->lane_break = false;
+  r->cur_buf = r->prev_buf = -1;
+  r->cbuf1_off = 0;
+  if (r->set_lane && r->set_lane(r->dev, -1) == 0 && r->set_words && !raster && !compact && !r->pq && r->local_tiles > 0 &&
+      !(p->flags & (RT_RENDER_COUNTERS | RT_RENDER_INSTRUMENTED)) && !std::getenv("RT_TILE_LIMIT")) {
+    uint64_t addr1 = 0;
+    if (r->cbuf1 && r->cbuf1_bytes == r->cbuf_bytes) {
+      if (vx_mem_address(r->cbuf1, &addr1) != 0) return fail("vx_mem_address failed");
+    } else {
+      if (upload(r->dev, nullptr, r->cbuf_bytes, &r->cbuf1, &addr1)) return -1;
+      r->cbuf1_bytes = r->cbuf_bytes;
+    }
+    r->cbuf1_off = (uint32_t)addr1 - (uint32_t)a.cbuf_addr;
+    r->lanes = (r->cbuf1_off & ~RT_LW_CBUF_MASK) == 0;  // (the allocator's granule is 256 B)
+  }
   // the render arguments: one buffer for the renderer's life (its address,
   // the launches' STARTUP_ARG, stays put), rewritten in stream order behind
   // the setup just queued -- no wait for the device
@@ -1071,7 +1096,17 @@ int rt_renderer_set_list_policy(rt_renderer_h r, uint32_t defer_frames) {
   return 0;
 }
 
-int rt_render_start(rt_renderer_h r) {
+namespace {
+int render_start(rt_renderer_h r, bool sync);
+}
+
+int rt_render_start(rt_renderer_h r) { return render_start(r, false); }
+
+namespace {
+// sync: the frame of rt_render (start + wait) -- an ordinary launch into the
+// buffer in use: the synchronous path neither flips the framebuffer nor asks
+// for a lane, it is the path of the rounds before
+int render_start(rt_renderer_h r, bool sync) {
   if (!r || !r->configured) return fail("renderer not configured");
   // the moving light: the lists of a light that stayed for sl_defer frames
   // are queued before this frame (the frames before walked the BVH)
@@ -1090,8 +1125,20 @@ int rt_render_start(rt_renderer_h r) {
     std::memcpy(lw, r->arg.light, sizeof(r->arg.light));
     lw[3] = RT_LW_LIGHT | (r->sl_stale ? RT_LW_NO_SLIST : 0u);
   }
+  // frame overlap: this frame's buffer and lane are the other ones than the
+  // last frame's; with one buffer the frame is an ordinary launch into the
+  // buffer in use (the second one after rt_framebuffer_device handed it out)
+  const bool flip = r->lanes && !sync;
+  const int buf = r->cur_buf < 0 ? 0 : flip ? r->cur_buf ^ 1 : r->cur_buf;
+  if (buf) lw[3] |= r->cbuf1_off & RT_LW_CBUF_MASK;
   auto start = [&](vx_buffer_h img) {
-    return (!r->set_words || r->set_words(r->dev, lw, 4) == 0) && vx_start(r->dev, img, r->args) == 0;
+    if (r->set_words && r->set_words(r->dev, lw, 4) != 0) return false;
+    if (flip && !r->lane_break && r->set_lane(r->dev, buf) != 0) return false;
+    if (vx_start(r->dev, img, r->args) != 0) return false;
+    r->lane_break = false;
+    r->prev_buf = flip ? r->cur_buf : -1;  // (a frame into the buffer in use keeps no earlier one)
+    r->cur_buf = buf;
+    return true;
   };
   // counter rows only when the caller wants rt_render_stats' counts
   if (r->set_counters &&
@@ -1111,6 +1158,7 @@ int rt_render_start(rt_renderer_h r) {
   vx_buffer_h img = bvh ? r->krnl_bvh[k] : r->krnl[mode][k];
   return start(img) ? 0 : fail("vx_start failed");
 }
+}  // namespace
 
 int rt_render_wait(rt_renderer_h r) {
   if (!r) return fail("null argument");
@@ -1118,7 +1166,7 @@ int rt_render_wait(rt_renderer_h r) {
 }
 
 int rt_render(rt_renderer_h r) {
-  int e = rt_render_start(r);
+  int e = render_start(r, true);
   return e ? e : rt_render_wait(r);
 }
 
@@ -1176,7 +1224,16 @@ int rt_render_run_totals(rt_renderer_h r, double* kernel_ms_sum, uint64_t* timed
 int rt_read_framebuffer(rt_renderer_h r, uint32_t* out, uint64_t count) {
   if (!r || !out || !r->configured) return fail("renderer not configured");
   if (count * 4 < r->cbuf_bytes) return fail("buffer too small");
-  return vx_copy_from_dev(out, r->cbuf, 0, r->cbuf_bytes) == 0 ? 0 : fail("vx_copy_from_dev failed");
+  vx_buffer_h b = r->cur_buf == 1 ? r->cbuf1 : r->cbuf;
+  return vx_copy_from_dev(out, b, 0, r->cbuf_bytes) == 0 ? 0 : fail("vx_copy_from_dev failed");
+}
+
+int rt_read_framebuffer_prev(rt_renderer_h r, uint32_t* out, uint64_t count) {
+  if (!r || !out || !r->configured) return fail("renderer not configured");
+  if (count * 4 < r->cbuf_bytes) return fail("buffer too small");
+  if (r->prev_buf < 0) return fail("no earlier frame is kept (one framebuffer, or fewer than two frames)");
+  vx_buffer_h b = r->prev_buf == 1 ? r->cbuf1 : r->cbuf;
+  return vx_copy_from_dev(out, b, 0, r->cbuf_bytes) == 0 ? 0 : fail("vx_copy_from_dev failed");
 }
 
 int rt_read_depthbuffer(rt_renderer_h r, uint32_t* out, uint64_t count) {
@@ -1239,7 +1296,12 @@ int rt_render_gather(rt_renderer_h r, struct rt_shard_comm* comm, uint32_t* imag
 int rt_framebuffer_device(rt_renderer_h r, void** ptr, uint64_t* bytes) {
   if (!r || !ptr || !r->configured || !r->mem_ptr) return fail("not available");
   if (bytes) *bytes = r->cbuf_bytes;
-  return r->mem_ptr(r->cbuf, ptr) == 0 ? 0 : fail("vx_hip_mem_ptr failed");
+  // the caller's pointer names one buffer: from here to the next configure
+  // every frame renders into it -- the last started frame's -- as an ordinary
+  // launch on lane 0, behind the frames in flight on both lanes
+  r->lanes = false;
+  r->prev_buf = -1;
+  return r->mem_ptr(r->cur_buf == 1 ? r->cbuf1 : r->cbuf, ptr) == 0 ? 0 : fail("vx_hip_mem_ptr failed");
 }
 
 int rt_device_stream(rt_renderer_h r, void** stream) {

@@ -106,6 +106,22 @@ struct rt_renderer {
   vx_buffer_h setup_krnl = nullptr, verts = nullptr, pdc = nullptr, dcz = nullptr;
   vx_buffer_h layer_list = nullptr, geometry_list = nullptr, vis = nullptr;
   uint64_t cbuf_bytes = 0;
+  // frame overlap (vx_rt.h rt_render_start): while `lanes` is set, frame n
+  // renders into framebuffer n mod 2 (cbuf, cbuf1) on the driver's launch
+  // lane n mod 2, so frames sharing a buffer share a lane and stay ordered.
+  // cur_buf: the buffer of the last started frame (-1: none since the
+  // configure); prev_buf: of the frame before it (-1: none, or one buffer)
+  vx_buffer_h cbuf1 = nullptr;
+  uint64_t cbuf1_bytes = 0;
+  uint32_t cbuf1_off = 0;   // cbuf1's arena offset minus cbuf's, mod 2^32 (RT_LW_CBUF_MASK bits)
+  bool lanes = false;
+  int cur_buf = -1, prev_buf = -1;
+  // setup launches were queued since the last frame (queue_lists): the next
+  // frame runs behind them as an ordinary launch -- with a rebuild before
+  // every frame nothing could overlap, and a lane per frame would only buy
+  // a cross-lane event each way
+  bool lane_break = false;
+  vx_hip_set_launch_lane_t set_lane = nullptr;
   rt_render_params_t params{};
   rt_kernel_arg_t arg{};
   bool configured = false;
@@ -135,7 +151,7 @@ struct rt_renderer {
     vx_buffer_h* bufs[] = {&krnl[0][0], &krnl[0][1], &krnl[1][0], &krnl[1][1], &krnl[2][0],
                            &krnl[2][1], &krnl[3][0], &nodes, &nodes4, &tris, &layers, &dcs, &tex,
                            &ptris, &geom, &oms, &bbox, &zbuf, &order, &vnodes, &vtris, &vlayers,
-                           &vgeom, &gather_recv, &gather_image, &prims, &cbuf, &args,
+                           &vgeom, &gather_recv, &gather_image, &prims, &cbuf, &cbuf1, &args,
                            &setup_krnl, &verts, &pdc, &dcz, &layer_list, &geometry_list, &vis,
                            &blist, &bidx, &cdesc, &sidx, &slist, &krnl_pq[0][0], &krnl_pq[0][1],
                            &krnl_pq[1][0], &krnl_pq[1][1], &pathq, &pathq_ctr,

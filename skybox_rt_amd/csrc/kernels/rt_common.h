@@ -61,6 +61,11 @@
 // in its dispatch packet, not through a copy into the argument block
 #define RT_LW_LIGHT    0x1u  // w[0..2] is the light (over arg.light)
 #define RT_LW_NO_SLIST 0x2u  // the light-space lists are stale: shadow rays walk the BVH
+// w[3] bits 8-31: the frame's framebuffer as an arena offset past arg.cbuf_addr, mod 2^32,
+// in the allocator's 256-B units (0: cbuf itself) -- two consecutive frames on the driver's
+// two launch lanes write apart.  In the launch word: rt_kernel_arg_t stays as it was;
+// added at the framebuffer stores (rt_trace.h store_out)
+#define RT_LW_CBUF_MASK 0xffffff00u
 
 #define RT_DC_DEPTH   0x1u
 #define RT_DC_COLOR   0x2u

@@ -100,6 +100,7 @@ struct Scene {
   uint32_t blist, bidx, blist_blocks;  // per-block candidate lists (rt_bentry_t)
   uint32_t sidx, slist, slist_on, slist_n;  // light-space shadow lists (rt_common.h)
   uint32_t cdesc, cdesc_first;  // chunk descriptor table (RT_CHUNK_DESC; cdesc 0: none)
+  uint32_t lw3;  // launch word 3 as it came (RT_LW_CBUF_MASK: the frame's framebuffer, store_out)
 };
 // sizeof(Scene) past the arena descriptor: walk_scene() copies the fields one
 // by one and asserts this size, so a new field cannot be left out unnoticed
@@ -111,7 +112,12 @@ struct Scene {
 // instead of VGPR + readfirstlane.
 //
 // The frame's launch words (rt_common.h RT_LW_*), kernel arguments like the
-// tag, override the block's light and switch stale lists off.
+// tag, override the block's light, switch stale lists off and select the
+// frame's framebuffer: the chunk descriptors stay relative to cbuf, and the
+// store sites add the word's offset bits (store_out) -- the word is kept as
+// it came, a kernel argument the compiler may read again where it is used;
+// cbuf + offset formed here instead stayed live across the chunk loop and
+// cost rt_kernel 24 more SGPR spills and 36 B of scratch.
 __device__ __forceinline__ Scene load_scene(const rt_kernel_arg_t* ga, const vx_launch_words_t& lw) {
   const uint64_t p = (uint64_t)ga;
   // (readfirstlane returns int: through uint32_t, or the low word sign-extends)
@@ -177,6 +183,7 @@ __device__ __forceinline__ Scene load_scene(const rt_kernel_arg_t* ga, const vx_
     s.light[2] = __builtin_bit_cast(float, lw.w[2]);
   }
   if (lw.w[3] & RT_LW_NO_SLIST) s.slist_on = 0;
+  s.lw3 = lw.w[3];
 #if RT_CHUNK_DESC
   s.cdesc = (uint32_t)a->cdesc_addr;
   s.cdesc_first = a->cdesc_first;
@@ -206,7 +213,7 @@ __device__ __forceinline__ Scene walk_scene(const Scene& S) {
   RT_COPY(shard_count) RT_COPY(tiles_x) RT_COPY(clear_color) RT_COPY(bounces) RT_COPY(seed)
   RT_COPY(split_tiles) RT_COPY(split_log) RT_COPY(tiles_x_magic) RT_COPY(num_tasks) RT_COPY(argp) RT_COPY(blist)
   RT_COPY(bidx) RT_COPY(blist_blocks) RT_COPY(sidx) RT_COPY(slist) RT_COPY(slist_on) RT_COPY(slist_n)
-  RT_COPY(cdesc) RT_COPY(cdesc_first)
+  RT_COPY(cdesc) RT_COPY(cdesc_first) RT_COPY(lw3)
 #undef RT_COPY
   // (the walks shoot no ray of their own: primary_dir / shadow_ray's fields stay out of the copy)
   w.sx = w.sy = w.light[0] = w.light[1] = w.light[2] = 0.0f;
@@ -1757,7 +1764,7 @@ __device__ __forceinline__ void chunk_pixel(const Scene& S, const ChunkMap& m, u
   *out = (rt_usgpr(S.flags) & RT_FLAG_COMPACT) ? (m.lt << 10) | ((*y & 31u) << 5) | (px & 31u) : *y * S.width + px;
 }
 __device__ __forceinline__ void store_out(const Scene& S, uint32_t out, uint32_t color) {
-  S.A.st_u32(S.cbuf + 4u * out, color);
+  S.A.st_u32(S.cbuf + (S.lw3 & RT_LW_CBUF_MASK) + 4u * out, color);
 }
 
 __device__ __forceinline__ void primary_dir(const Scene& S, uint32_t x, uint32_t y, Ray& r) {
@@ -1830,7 +1837,7 @@ __device__ __forceinline__ void store_pixel(const Scene& S, uint32_t t, uint32_t
     const TaskPix m = task_map(S, t);
     idx = (m.lt << 10) | ((y & 31u) << 5) | (x & 31u);
   }
-  S.A.st_u32(S.cbuf + 4u * idx, color);
+  S.A.st_u32(S.cbuf + (S.lw3 & RT_LW_CBUF_MASK) + 4u * idx, color);
 }
 
 

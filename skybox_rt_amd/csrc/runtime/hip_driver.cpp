@@ -16,12 +16,26 @@
 //                       timeout (the simx driver polls a std::future at 1 s).
 //                       simx's start() first waits for the in-flight run
 //                       (vortex.cpp:174-176); here a start() behind a run
-//                       queues on the stream instead -- the device still runs
-//                       them one after the other, the host just does not
-//                       idle between them (VX_HIP_QUEUE_DEPTH runs in flight,
-//                       default 2; 1 = simx's synchronous behaviour).  Every
+//                       queues on the stream instead -- the device runs them
+//                       one after the other, the host just does not idle
+//                       between them (VX_HIP_QUEUE_DEPTH runs in flight,
+//                       default 2; 1 = simx's synchronous behaviour).  A
+//                       start() that asked for a launch lane
+//                       (vx_hip_set_launch_lane; env VX_HIP_OVERLAP=1) queues
+//                       on that lane's stream -- lane 0 is the driver's
+//                       stream, lane 1 a second one -- behind the earlier
+//                       launches of its lane only, so two consecutive frames
+//                       on lanes 0 and 1 may be resident together: the next
+//                       frame's first waves fill the slots the last waves of
+//                       this one leave empty.  Everything else (a start()
+//                       without a lane, the synchronous start + wait with
+//                       its completion kernel, a launch group, every copy) is
+//                       an ordinary operation on lane 0 and stays ordered
+//                       against both lanes by one event per change of
+//                       regime (lanes.h); frames alternating 0, 1, 0, 1
+//                       record none.  Every
 //                       call that touches memory, DCRs or counters still
-//                       waits for all of them first.  Queued runs carry HIP
+//                       waits for all runs, on both lanes, first.  Queued runs carry HIP
 //                       events (kernel time) one in VX_HIP_TIME_EVERY (4);
 //                       a run started on an idle queue (the apps' start +
 //                       wait) is followed by its image's completion kernel
@@ -59,6 +73,7 @@
 #include "arena.h"
 #include "callbacks.h"
 #include "common.h"
+#include "lanes.h"
 #include "vortex_hip.h"
 
 #define HIP_CHECK(_expr)                                                              \
@@ -84,6 +99,8 @@ constexpr int kGridWavesPerCU = 64;  // 4x the 16 resident waves/CU of the RT ke
 // kHostMemApp, then one 64-B completion slot per in-flight run (<entry>_done:
 // nonce, start and end stamps)
 constexpr uint64_t kHostMemBytes = 65536, kHostMemApp = 32768, kTailSlot = 64;
+// VX_HIP_OVERLAP when the environment does not set it
+constexpr uint64_t kOverlapDefault = 1;
 
 uint64_t env_u64(const char* name, uint64_t dflt) {
   const char* s = std::getenv(name);
@@ -163,6 +180,7 @@ class vx_device {
 
   ~vx_device() {
     if (stream_) (void)hipStreamSynchronize(stream_);
+    if (lane1_) (void)hipStreamSynchronize(lane1_);
     for (auto& kv : modules_) (void)hipModuleUnload(kv.second.module);
     for (int i = 0; i < kMaxQueue; ++i) {
       if (ev_start_[i]) (void)hipEventDestroy(ev_start_[i]);
@@ -172,6 +190,9 @@ class vx_device {
       if (stage_ev_[i]) (void)hipEventDestroy(stage_ev_[i]);
     if (stage_) (void)hipHostFree(stage_);
     if (hostmem_) (void)hipHostFree(hostmem_);
+    for (hipEvent_t e : join_ev_)
+      if (e) (void)hipEventDestroy(e);
+    if (lane1_) (void)hipStreamDestroy(lane1_);
     if (stream_) (void)hipStreamDestroy(stream_);
     if (arena_) (void)hipFree(arena_);
   }
@@ -210,6 +231,12 @@ class vx_device {
     launch_mode_timed_ = launch_mode_;
     counters_env_ = env_u64("VX_HIP_COUNTERS", 0) != 0;
     tail_on_ = env_u64("VX_HIP_TAIL", 1) != 0;
+    // launch lanes (lanes.h): with VX_HIP_OVERLAP=1 a launch may run on lane
+    // 1 (its stream is opened by the first launch that goes there: a device
+    // that only ever runs synchronous frames keeps to the one stream of the
+    // rounds before); without it every launch is an ordinary one
+    overlap_on_ = env_u64("VX_HIP_OVERLAP", kOverlapDefault) != 0;
+    order_ = vxlanes::LaneOrder(overlap_on_);
     return 0;
   }
 
@@ -276,6 +303,7 @@ class vx_device {
     wait_idle();
     HIP_CHECK(hipMemcpyAsync(arena_ + addr, src, size, hipMemcpyHostToDevice, stream_));
     HIP_CHECK(hipStreamSynchronize(stream_));
+    order_.lane0_idle();
     for (auto& kv : shadow_) {  // keep kernel-image shadows coherent
       const uint64_t a = kv.first, e = a + kv.second.size();
       if (addr >= a && addr + size <= e) {
@@ -301,8 +329,11 @@ class vx_device {
     if (stage_busy_[slot]) HIP_CHECK(hipEventSynchronize(stage_ev_[slot]));
     uint8_t* st = stage_ + (size_t)slot * kStageSlot;
     std::memcpy(st, src, size);
-    HIP_CHECK(hipMemcpyAsync(arena_ + addr, st, size, hipMemcpyHostToDevice, stream_));
-    HIP_CHECK(hipEventRecord(stage_ev_[slot], stream_));
+    // behind the launches of both lanes, before every launch issued after it
+    hipStream_t ls = nullptr;
+    if (lane_stream(order_.ordinary(), &ls) != 0) return -1;
+    HIP_CHECK(hipMemcpyAsync(arena_ + addr, st, size, hipMemcpyHostToDevice, ls));
+    HIP_CHECK(hipEventRecord(stage_ev_[slot], ls));
     stage_busy_[slot] = true;
     return 0;
   }
@@ -312,6 +343,7 @@ class vx_device {
     wait_idle();
     HIP_CHECK(hipMemcpyAsync(dst, arena_ + addr, size, hipMemcpyDeviceToHost, stream_));
     HIP_CHECK(hipStreamSynchronize(stream_));
+    order_.lane0_idle();
     return 0;
   }
 
@@ -319,6 +351,8 @@ class vx_device {
     // DCR writes already waited for the device (dcr_write); the STARTUP
     // words below only differ from the in-flight run's when another image
     // or argument block is started, which the constant upload check catches
+    const int want_lane = launch_lane_;  // vx_hip_set_launch_lane: this start() only
+    launch_lane_ = -1;
     if (depth_ <= 1) wait_idle();
     dcr_set(VX_DCR_BASE_STARTUP_ADDR0, (uint32_t)(krnl_addr & 0xffffffffu));
     dcr_set(VX_DCR_BASE_STARTUP_ADDR1, (uint32_t)(krnl_addr >> 32));
@@ -343,6 +377,10 @@ class vx_device {
       uint64_t j = retired_ + 1;
       while (j <= issued_ && !timed_[(j - 1) % kMaxQueue]) ++j;
       if (retire(j <= issued_ ? j : issued_, VX_MAX_TIMEOUT) != 0) return -1;
+    }
+    if (upload) {  // the constant copies below: ordinary operations on lane 0, ahead of this launch on either lane
+      hipStream_t s0 = nullptr;
+      if (lane_stream(order_.ordinary(), &s0) != 0) return -1;
     }
     if (!m->base_set) {
       m->base_value = (uint64_t)(uintptr_t)arena_;
@@ -378,6 +416,20 @@ class vx_device {
     // device's own stamps (launch_probe: +6.6 vs +14.5 us over the kernel)
     const bool tail = tail_on_ && m->done && group_n_ == 1 && !group_untimed_ && launch_mode_ != 2 &&
                       issued_ == retired_ && ensure_hostmem() == 0;
+    // the launch's lane: the one it asked for when it is a single launch;
+    // the launches of a group, and the launch of a synchronous start + wait
+    // that its completion kernel follows, are ordinary operations on lane 0.
+    // (A laned launch on an idle queue needs no wait either: the host saw
+    // both lanes run empty, lanes.h.)  The cross-lane wait, if this launch
+    // changes the regime, is queued here.
+    // Not with counter rows on (vx_hip_set_counters, VX_HIP_COUNTERS,
+    // VORTEX_PROFILING): the rows of two launches in flight would mix.
+    const bool laned = want_lane >= 0 && group_n_ == 1 && !tail && !rows;
+    const vxlanes::Step step = laned ? order_.laned(want_lane) : order_.ordinary();
+    if (step.lane == 1 && ensure_lane1() != 0) return -1;
+    hipStream_t ls = nullptr;
+    if (lane_stream(step, &ls) != 0) return -1;
+    lane_[slot] = (uint8_t)step.lane;
     if (first) {
       group_timed_ = !group_untimed_ && launch_mode_ != 2 &&
                      (issued_ == retired_ || runs_issued_ % time_every_ == 0);
@@ -398,7 +450,7 @@ class vx_device {
     }
     if (tail) {
       HIP_CHECK(hipExtModuleLaunchKernel(m->entry, m->grid * m->block, 1, 1, m->block, 1, 1, 0,
-                                         stream_, kparams, nullptr, nullptr, nullptr, 0));
+                                         ls, kparams, nullptr, nullptr, nullptr, 0));
       const uint32_t nonce = ++tail_nonce_;
       tail_nonce_slot_[slot] = nonce;
       volatile uint32_t* w = tail_word(slot);
@@ -406,25 +458,25 @@ class vx_device {
       uint64_t hp = hostmem_dev_ + kHostMemApp + (uint64_t)slot * kTailSlot;
       uint32_t nv = nonce;
       void* dparams[2] = {&hp, &nv};
-      HIP_CHECK(hipModuleLaunchKernel(m->done, 1, 1, 1, 64, 1, 1, 0, stream_, dparams, nullptr));
+      HIP_CHECK(hipModuleLaunchKernel(m->done, 1, 1, 1, 64, 1, 1, 0, ls, dparams, nullptr));
     } else if (!timed) {
       HIP_CHECK(hipExtModuleLaunchKernel(m->entry, m->grid * m->block, 1, 1, m->block, 1, 1, 0,
-                                         stream_, kparams, nullptr, nullptr, nullptr, 0));
+                                         ls, kparams, nullptr, nullptr, nullptr, 0));
     } else if (launch_mode_ == 2) {
       HIP_CHECK(hipExtModuleLaunchKernel(m->entry, m->grid * m->block, 1, 1, m->block, 1, 1, 0,
-                                         stream_, kparams, nullptr, nullptr, nullptr, 0));
+                                         ls, kparams, nullptr, nullptr, nullptr, 0));
     } else if (launch_mode_ == 1) {
       // the dispatch packet itself carries the start/stop timestamps: no
       // separate event packets between back-to-back frames
       HIP_CHECK(hipExtModuleLaunchKernel(m->entry, m->grid * m->block, 1, 1, m->block, 1, 1, 0,
-                                         stream_, kparams, nullptr,
+                                         ls, kparams, nullptr,
                                          first ? ev_start_[slot] : nullptr,
                                          last ? ev_stop_[slot] : nullptr, 0));
     } else {
-      if (first) HIP_CHECK(hipEventRecord(ev_start_[slot], stream_));
-      HIP_CHECK(hipModuleLaunchKernel(m->entry, m->grid, 1, 1, m->block, 1, 1, 0, stream_,
+      if (first) HIP_CHECK(hipEventRecord(ev_start_[slot], ls));
+      HIP_CHECK(hipModuleLaunchKernel(m->entry, m->grid, 1, 1, m->block, 1, 1, 0, ls,
                                       kparams, nullptr));
-      if (last) HIP_CHECK(hipEventRecord(ev_stop_[slot], stream_));
+      if (last) HIP_CHECK(hipEventRecord(ev_stop_[slot], ls));
     }
     ++issued_;
     mpm_dirty_ = true;  // read back lazily by mpm_query (after wait_idle)
@@ -450,45 +502,74 @@ class vx_device {
     if (!by_event && !by_tail) upto = issued_;
     hipEvent_t stop = ev_stop_[(upto - 1) % kMaxQueue];
     const auto t0 = std::chrono::steady_clock::now();
-    for (uint32_t spin = 0;; ++spin) {
-      if (by_tail) {
-        if (*tail_word(us) == tail_nonce_slot_[us]) break;
-        // (no HIP call on this path: a fault still ends the wait at the timeout)
-        const auto dt = std::chrono::steady_clock::now() - t0;
-        if ((uint64_t)std::chrono::duration_cast<std::chrono::milliseconds>(dt).count() > timeout_ms) {
-          const hipError_t e = hipStreamQuery(stream_);
-          if (e != hipSuccess && e != hipErrorNotReady) {
-            std::printf("[VXDRV] kernel failed: %s\n", hipGetErrorString(e));
-            retired_ = issued_;
-          }
+    // poll a HIP completion query until it succeeds (0), fails or times out (-1)
+    auto poll = [&](auto&& query) -> int {
+      for (uint32_t spin = 0;; ++spin) {
+        const hipError_t e = query();
+        if (e == hipSuccess) return 0;
+        if (e != hipErrorNotReady) {
+          std::printf("[VXDRV] kernel failed: %s\n", hipGetErrorString(e));
+          retired_ = issued_;
           return -1;
         }
-        if (spin > 4096 && dt > std::chrono::milliseconds(5)) {
-          // a long run: check the stream for a fault now and then, then sleep
-          const hipError_t e = hipStreamQuery(stream_);
-          if (e != hipSuccess && e != hipErrorNotReady) {
-            std::printf("[VXDRV] kernel failed: %s\n", hipGetErrorString(e));
-            retired_ = issued_;
-            return -1;
-          }
+        const auto dt = std::chrono::steady_clock::now() - t0;
+        if ((uint64_t)std::chrono::duration_cast<std::chrono::milliseconds>(dt).count() > timeout_ms)
+          return -1;
+        // spin (a frame is ~0.1 ms; a sleep costs its timer slack, ~60 us),
+        // back off to sleeping only for long runs
+        if (spin > 1024 && dt > std::chrono::milliseconds(5))
           std::this_thread::sleep_for(std::chrono::microseconds(50));
-        }
-        continue;
       }
-      hipError_t e = by_event ? hipEventQuery(stop) : hipStreamQuery(stream_);
-      if (e == hipSuccess) break;
-      if (e != hipErrorNotReady) {
-        std::printf("[VXDRV] kernel failed: %s\n", hipGetErrorString(e));
-        retired_ = issued_;
-        return -1;
-      }
+    };
+    // (a completion kernel only follows a run started on an idle queue, lane 0)
+    for (uint32_t spin = 0; by_tail; ++spin) {
+      if (*tail_word(us) == tail_nonce_slot_[us]) break;
+      // (no HIP call on this path: a fault still ends the wait at the timeout)
       const auto dt = std::chrono::steady_clock::now() - t0;
-      if ((uint64_t)std::chrono::duration_cast<std::chrono::milliseconds>(dt).count() > timeout_ms)
+      if ((uint64_t)std::chrono::duration_cast<std::chrono::milliseconds>(dt).count() > timeout_ms) {
+        const hipError_t e = hipStreamQuery(stream_);
+        if (e != hipSuccess && e != hipErrorNotReady) {
+          std::printf("[VXDRV] kernel failed: %s\n", hipGetErrorString(e));
+          retired_ = issued_;
+        }
         return -1;
-      // spin (a frame is ~0.1 ms; a sleep costs its timer slack, ~60 us),
-      // back off to sleeping only for long runs
-      if (spin > 1024 && dt > std::chrono::milliseconds(5))
+      }
+      if (spin > 4096 && dt > std::chrono::milliseconds(5)) {
+        // a long run: check the stream for a fault now and then, then sleep
+        const hipError_t e = hipStreamQuery(stream_);
+        if (e != hipSuccess && e != hipErrorNotReady) {
+          std::printf("[VXDRV] kernel failed: %s\n", hipGetErrorString(e));
+          retired_ = issued_;
+          return -1;
+        }
         std::this_thread::sleep_for(std::chrono::microseconds(50));
+      }
+    }
+    if (by_event) {
+      if (poll([&] { return hipEventQuery(stop); }) != 0) return -1;
+      // the event says nothing about the other lane: the newest run up to
+      // `upto` over there, by its own event or by its stream running empty.
+      // (Conservative: with one run in time_every_ timed and the frames
+      // alternating lanes, the timed runs fall on one lane and the other is
+      // waited for by its stream, newer runs than `upto` included -- the
+      // host then keeps fewer runs queued than the depth bound allows.  The
+      // untimed mode of a timed loop, vx_hip_set_timing(0), has no bound.)
+      const int own = lane_[us];
+      for (uint64_t j = upto - 1; lane1_ && j > retired_; --j) {
+        const int js = (int)((j - 1) % kMaxQueue);
+        if (lane_[js] == own) continue;
+        hipStream_t other = lane_[js] ? lane1_ : stream_;
+        const bool ev = timed_[js] && !tail_[js];
+        if (poll([&] { return ev ? hipEventQuery(ev_stop_[js]) : hipStreamQuery(other); }) != 0) return -1;
+        break;
+      }
+      if (upto == issued_) order_.lane1_idle();  // no launch is left in flight on either lane
+    } else if (!by_tail) {
+      // both lanes run empty
+      if (poll([&] { return hipStreamQuery(stream_); }) != 0) return -1;
+      order_.lane0_idle();
+      if (lane1_ && poll([&] { return hipStreamQuery(lane1_); }) != 0) return -1;
+      order_.lane1_idle();
     }
     for (; retired_ < upto; ++retired_) {
       const int slot = (int)(retired_ % kMaxQueue);
@@ -607,6 +688,14 @@ class vx_device {
     group_untimed_ = untimed;
     return 0;
   }
+  // the lane the next start() asks for (vx_hip_set_launch_lane); -1: none.
+  // Fails while the device has one lane (VX_HIP_OVERLAP=0): the caller then
+  // keeps to one buffer and ordinary launches.
+  int set_launch_lane(int lane) {
+    if (!overlap_on_ || lane < -1 || lane >= vxlanes::kLanes) return -1;
+    launch_lane_ = lane;
+    return 0;
+  }
   void set_launch_tag(uint32_t tag) { launch_tag_ = tag; }  // the next start()'s kernel argument
   void set_launch_words(const uint32_t* w, uint32_t n) {       // and its launch words
     std::memset(launch_words_, 0, sizeof(launch_words_));
@@ -674,6 +763,23 @@ class vx_device {
   }
   void wait_idle() {
     if (issued_ > retired_) ready_wait(VX_MAX_TIMEOUT);
+  }
+  // the stream of an operation placed by lanes.h, behind the cross-lane wait
+  // it asked for: one event recorded on the lane waited for
+  int ensure_lane1() {
+    if (lane1_) return 0;
+    HIP_CHECK(hipStreamCreateWithFlags(&lane1_, hipStreamNonBlocking));
+    for (hipEvent_t& e : join_ev_) HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    return 0;
+  }
+  int lane_stream(const vxlanes::Step& s, hipStream_t* out) {
+    hipStream_t st[vxlanes::kLanes] = {stream_, lane1_};
+    if (s.wait_for >= 0) {
+      HIP_CHECK(hipEventRecord(join_ev_[s.wait_for], st[s.wait_for]));
+      HIP_CHECK(hipStreamWaitEvent(st[s.lane], join_ev_[s.wait_for], 0));
+    }
+    *out = st[s.lane];
+    return 0;
   }
 
   int load_module(uint64_t krnl_addr, Module** out) {
@@ -770,7 +876,15 @@ class vx_device {
   uint32_t launch_tag_ = 0;
   uint32_t launch_words_[4] = {};
   std::map<uint64_t, uint64_t> image_key_;  // image address -> module key
-  hipStream_t stream_ = nullptr;
+  hipStream_t stream_ = nullptr;  // lane 0
+  // launch lanes (lanes.h): the second stream, one join event per lane waited
+  // for, the lane the next start() asked for and the lane of every queued run
+  hipStream_t lane1_ = nullptr;
+  bool overlap_on_ = false;
+  hipEvent_t join_ev_[vxlanes::kLanes] = {};
+  vxlanes::LaneOrder order_{false};
+  int launch_lane_ = -1;
+  uint8_t lane_[64] = {};
   static constexpr int kMaxQueue = 64;  // >= (depth_ + time_every_) * group_n_
   static_assert(kHostMemApp + (uint64_t)kMaxQueue * kTailSlot <= kHostMemBytes,
                 "a completion slot per queue slot in the pinned block");
@@ -992,6 +1106,10 @@ __attribute__((visibility("default"))) int vx_hip_set_launch_tag(vx_device_h hde
   if (hdevice == nullptr) return -1;
   ((vx_device*)hdevice)->set_launch_tag(tag);
   return 0;
+}
+__attribute__((visibility("default"))) int vx_hip_set_launch_lane(vx_device_h hdevice, int lane) {
+  if (hdevice == nullptr) return -1;
+  return ((vx_device*)hdevice)->set_launch_lane(lane);
 }
 __attribute__((visibility("default"))) int vx_hip_device_id(vx_device_h hdevice, int* id) {
   if (hdevice == nullptr || id == nullptr) return -1;

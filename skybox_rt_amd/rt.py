@@ -130,6 +130,7 @@ def lib():
                                      C.POINTER(C.c_uint64)],
             "rt_render_set_timing": [vp, C.c_int],
             "rt_read_framebuffer": [vp, vp, u64],
+            "rt_read_framebuffer_prev": [vp, vp, u64],
             "rt_read_depthbuffer": [vp, vp, u64],
             "rt_launch_rows": [vp, vp, u64, C.POINTER(u64)],
             "rt_scene_setup_prims": [vp, u32, u32, vp, u64],
@@ -439,6 +440,15 @@ class Renderer:
             return out[:n]
         out = np.zeros((p.height, p.width), np.uint32)
         _check(lib().rt_read_framebuffer(self._h, out.ctypes.data, out.size), "rt_read_framebuffer")
+        return out
+
+    def framebuffer_prev(self) -> np.ndarray:
+        """The frame started before the last one (overlapped configurations
+        keep two framebuffers; an error when only one frame is kept)."""
+        p = self.params
+        out = np.zeros((p.height, p.width), np.uint32)
+        _check(lib().rt_read_framebuffer_prev(self._h, out.ctypes.data, out.size),
+               "rt_read_framebuffer_prev")
         return out
 
     def launch_rows(self) -> np.ndarray:
