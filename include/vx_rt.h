@@ -94,6 +94,31 @@ int rt_scene_load(const char* path, rt_scene_h* out);
 /* draw3d's -s start / -e end (tests/regression/draw3d/main.cpp:179-181): only
  * drawcalls start <= d <= end are drawn (rt_scene_load = 0, 0xffffffff) */
 int rt_scene_load_range(const char* path, uint32_t start_draw, uint32_t end_draw, rt_scene_h* out);
+/* rt_scene_load_range with flags.  RT_SCENE_OM_LAYERS: a scene the RT path
+ * cannot trace as a whole -- a drawcall blends, uses the stencil, masks colour
+ * channels, tests depth without writing it or with another function than the
+ * drawcalls before it, or is a depth-off layer after geometry -- is split at
+ * the first such drawcall.  The drawcalls before it (the traced head) are what
+ * the scene's geometry / layer sets, its BVH and rt_scene_info describe; that
+ * drawcall and every one after it, whatever their states, are the ordered
+ * tail.  Plain and RT_RENDER_SHADOWS frames of such a scene trace the head as
+ * always (raster-exact primary visibility, layers, shading, one shadow ray per
+ * geometry hit, the head's depth-tested primitives the only occluders) and then
+ * fold every tail primitive that covers a pixel over the pixel's colour and
+ * depth/stencil word in ascending primitive index through the output merger
+ * (depth/stencil test, blending, write masks), one launch of rt_om_kernel.hip
+ * that stores each pixel once.  Without shadows that is the raster pipeline's
+ * frame of the whole scene; tail fragments cast no shadow rays and occlude
+ * none.  A scene with an empty tail behaves as if loaded without the flag.
+ * Without the flag (rt_scene_load, rt_scene_load_range) nothing changes: such
+ * a scene is unsupported on the RT path and renders with RT_RENDER_RASTER. */
+#define RT_SCENE_OM_LAYERS 0x1u
+int rt_scene_load_ex(const char* path, uint32_t start_draw, uint32_t end_draw, uint32_t flags,
+                     rt_scene_h* out);
+/* the split of a scene loaded with RT_SCENE_OM_LAYERS: the first drawcall of
+ * the ordered tail (num_drawcalls when the tail is empty or the flag was not
+ * given) and the tail's primitive count */
+int rt_scene_om_split(rt_scene_h scene, uint32_t* first_tail_drawcall, uint32_t* tail_prims);
 int rt_scene_free(rt_scene_h scene);
 int rt_scene_info(rt_scene_h scene, rt_scene_info_t* info);
 /* flattened triangles, float[num_prims][3][10] (x,y,z,w, r,g,b,a, u,v) */
@@ -119,11 +144,27 @@ int rt_scene_setup_vis(rt_scene_h scene, uint32_t width, uint32_t height, uint32
 int rt_scene_vis_tree(rt_scene_h scene, uint32_t width, uint32_t height, float depth_scale,
                       int32_t* refs, uint32_t* num_nodes, int32_t* leaf_pids, uint32_t* num_leaf,
                       uint32_t* stack4);
+/* the ordered tail's per-block lists at width x height, one shard (what
+ * rt_renderer_configure builds and uploads, app/vis.h BuildTailLists): for
+ * every 8x8 block -- block (tile row * tiles per row + tile column) * 16 +
+ * (by & 3) * 4 + (bx & 3), RT_REC_BIDX's numbering -- idx[2] = first entry and
+ * count, ent = the primitive indices of the tail primitives whose
+ * covered-pixel rectangle reaches the block, ascending.  NULL arrays: sizes
+ * only.  NO REFERENCE. */
+int rt_scene_setup_olists(rt_scene_h scene, uint32_t width, uint32_t height, uint32_t* idx, uint32_t* ent,
+                          uint64_t* entries, uint64_t* blocks);
 
 /* kernel_dir: directory holding rt_kernel.vxbin / rt_kernel_stats.vxbin
  * (NULL = next to librtapp.so).  Opens its own vortex device.  Scenes the
- * RT path cannot trace (blending, stencil, layers after geometry) get a
- * renderer that accepts only RT_RENDER_RASTER. */
+ * RT path cannot trace as a whole (blending, stencil, layers after geometry)
+ * get a renderer that accepts only RT_RENDER_RASTER (configure returns -2
+ * otherwise) -- unless the scene was loaded with RT_SCENE_OM_LAYERS: then
+ * plain and RT_RENDER_SHADOWS frames (with RT_RENDER_COUNTERS, COMPACT,
+ * HOST_SETUP and shards as usual) trace the head and fold the ordered tail
+ * (image rt_om.vxbin; ordinary frames, one framebuffer, no frame overlap),
+ * RT_RENDER_RASTER works as ever, and RT_RENDER_PATH / FLAT / BVH_WALK /
+ * INSTRUMENTED, or a tree other than the binary16 BVH4 (the generic deep
+ * images' layouts: RT_RENDER_BVH2, env RT_BVH_F16=0), return -2. */
 int rt_renderer_create(rt_scene_h scene, const char* kernel_dir, rt_renderer_h* out);
 int rt_renderer_free(rt_renderer_h r);
 int rt_renderer_configure(rt_renderer_h r, const rt_render_params_t* params);
@@ -300,6 +341,8 @@ int rt_renderer_set_list_policy(rt_renderer_h r, uint32_t defer_frames);
 #define RT_REC_SLIST 13u    /* rt_tri_t per light-space list entry (+1 padding record) */
 #define RT_REC_CDESC 14u    /* rt_cdesc_t per chunk of the whole-block tier, as the device setup built it */
 #define RT_REC_CDESC_HOST 15u /* the same table restated on the host from the work order and list headers */
+#define RT_REC_OIDX 16u     /* ordered tail: uint32[2] per local 8x8 block: first list entry, count */
+#define RT_REC_OLIST 17u    /* ordered tail: u32 primitive index per entry (+2 padding entries, RT_OLIST_PAD) */
 int rt_renderer_export_records(rt_renderer_h r, uint32_t which, void* out, uint64_t bytes,
                                uint64_t* size);
 

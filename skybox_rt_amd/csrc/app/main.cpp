@@ -19,7 +19,10 @@
 // pipeline instead, which is what draw3d itself runs.  Extensions: -S shadow
 // rays, -L x,y,w light, -P N path tracing with N bounces, -F flat triangle
 // list, -R raster pipeline, -n N repeat launches, -B lbvh|sah device BVH
-// build, -H host-loop setup; multi-GPU (one process per GPU over
+// build, -H host-loop setup, -O load the scene with RT_SCENE_OM_LAYERS (a
+// scene the RT path cannot trace as a whole renders on the RT path all the
+// same: its head traced, its ordered tail folded through the output merger,
+// vx_rt.h); multi-GPU (one process per GPU over
 // librt_shard.so / RCCL): -G rank,ranks -I idfile -- this process renders
 // 32x32 tiles t with t % ranks == rank, rank 0 writes the RCCL communicator
 // id to `idfile` (the others wait for it), every frame ends with
@@ -64,6 +67,7 @@ int rank = -1, ranks = 1;            // -G rank,ranks
 const char* id_file = "rt_shard.id";  // -I
 const char* build = nullptr;          // -B lbvh|sah: build the BVH on the device
 bool host_setup = false;              // -H: per-resolution records by the host loops
+bool om_layers = false;               // -O: RT_SCENE_OM_LAYERS
 
 #ifdef RT_APP_RASTER
 const char* kOpts = "t:i:o:r:w:h:k:n:z?";
@@ -73,13 +77,14 @@ void usage() {
               "[-k tilelogsize] [-n repeat]\n");
 }
 #else
-const char* kOpts = "t:s:e:i:o:r:w:h:k:n:L:P:G:I:B:uxyzSRFH?";
+const char* kOpts = "t:s:e:i:o:r:w:h:k:n:L:P:G:I:B:uxyzSRFHO?";
 void usage() {
   std::printf("Vortex 3D Rendering Test (MI355X).\n"
               "Usage: [-t trace] [-s startdraw] [-e enddraw] [-o output] [-r reference] [-w width] "
               "[-h height] [-x s/w rast] [-y s/w om] [-u s/w tex] [-k tilelogsize]\n"
               "       [-S shadows] [-L x,y,w] [-n repeat] [-R raster | -P bounces | -F flat] "
               "[-G rank,ranks [-I idfile]] [-B lbvh|sah device BVH build] [-H host setup]\n"
+              "       [-O trace the head, fold blended / stencil / masked drawcalls (RT_SCENE_OM_LAYERS)]\n"
               "       env RT_KERNEL_DIR: kernel images; RT_ASSETS_PATHS: search directories\n");
 }
 #endif
@@ -119,6 +124,7 @@ int main(int argc, char** argv) {
     case 'I': id_file = optarg; break;
     case 'B': build = optarg; break;
     case 'H': host_setup = true; break;
+    case 'O': om_layers = true; break;
 #endif
     case '?': usage(); return 0;
     default: usage(); return -1;  // -i: in the reference's option string, never handled
@@ -170,7 +176,7 @@ int main(int argc, char** argv) {
   }
   const std::string trace = rt::ResolveAsset(trace_file, true);
   rt_scene_h scene = nullptr;
-  RT_CHECK(rt_scene_load_range(trace.c_str(), start_draw, end_draw, &scene));
+  RT_CHECK(rt_scene_load_ex(trace.c_str(), start_draw, end_draw, om_layers ? RT_SCENE_OM_LAYERS : 0u, &scene));
   rt_scene_info_t info;
   RT_CHECK(rt_scene_info(scene, &info));
   std::printf("CGL Trace: drawcalls=%u, primitives=%u, geometry=%u, layers=%u, textures=%u\n",
@@ -178,6 +184,13 @@ int main(int argc, char** argv) {
               info.num_textures);
   std::printf("BVH: nodes=%u, leaves=%u, depth=%u, build=%.3f ms (parse %.3f ms)\n",
               info.bvh_nodes, info.bvh_leaves, info.bvh_depth, info.bvh_ms, info.parse_ms);
+  if (om_layers) {
+    uint32_t first_tail = 0, tail_prims = 0;
+    RT_CHECK(rt_scene_om_split(scene, &first_tail, &tail_prims));
+    if (tail_prims)
+      std::printf("Ordered tail: drawcalls %u-%u (%u primitives) folded over the traced head\n", first_tail,
+                  info.num_drawcalls - 1, tail_prims);
+  }
   rt_renderer_h r = nullptr;
   RT_CHECK(rt_renderer_create(scene, std::getenv("RT_KERNEL_DIR"), &r));
   if (build) {

@@ -78,7 +78,38 @@ int rt_scene_load(const char* path, rt_scene_h* out) {
 }
 
 int rt_scene_load_range(const char* path, uint32_t start_draw, uint32_t end_draw, rt_scene_h* out) {
+  return rt_scene_load_ex(path, start_draw, end_draw, 0u, out);
+}
+
+// the first drawcall of the ordered tail: the first one that breaks a rule of
+// the classification below (blending / stencil / partial colour mask, a
+// depth-tested drawcall without depth writes or with a depth function other
+// than the one LESS / LEQUAL of the drawcalls before it, a screen layer after
+// geometry); the drawcall count when none does
+static uint32_t first_tail_drawcall(const rt::Scene& scene) {
+  bool seen_geom = false;
+  int geom_func = -1;
+  for (size_t d = 0; d < scene.drawcalls.size(); ++d) {
+    const rt::States& st = scene.drawcalls[d].states;
+    if (st.blend_enabled || st.stencil_test || (st.color_writemask & 0xf) != 0xf) return (uint32_t)d;
+    if (st.depth_test) {
+      const int f = (int)rt::ToVXCompare(st.depth_func);
+      if (!(st.depth_writemask & 1) || (f != VX_OM_DEPTH_FUNC_LESS && f != VX_OM_DEPTH_FUNC_LEQUAL) ||
+          (geom_func >= 0 && f != geom_func))
+        return (uint32_t)d;
+      geom_func = f;
+      seen_geom = true;
+    } else if (seen_geom) {
+      return (uint32_t)d;
+    }
+  }
+  return (uint32_t)scene.drawcalls.size();
+}
+
+int rt_scene_load_ex(const char* path, uint32_t start_draw, uint32_t end_draw, uint32_t flags,
+                     rt_scene_h* out) {
   if (path == nullptr || out == nullptr) return fail("null argument");
+  if (flags & ~RT_SCENE_OM_LAYERS) return fail("unknown scene flags");
   auto sc = std::make_unique<rt_scene>();
   auto t0 = std::chrono::steady_clock::now();
   std::string err;
@@ -101,12 +132,21 @@ int rt_scene_load_range(const char* path, uint32_t start_draw, uint32_t end_draw
   sc->parse_ms = ms_since(t0);
   // classify drawcalls (DESIGN.md "Scope"): screen layers (depth test off)
   // must precede geometry; geometry shares one LESS/LEQUAL depth function.
+  // RT_SCENE_OM_LAYERS: the drawcalls from the first rule breaker on are the
+  // ordered tail, folded over the traced head by rt_om_kernel; the loop
+  // below then classifies the head only (and finds nothing unsupported)
+  sc->first_tail_dc = (flags & RT_SCENE_OM_LAYERS) ? first_tail_drawcall(sc->scene)
+                                                   : (uint32_t)sc->scene.drawcalls.size();
   bool seen_geom = false;
   int geom_func = -1;
   std::vector<rt::BuildTri> build;
   for (size_t d = 0; d < sc->scene.drawcalls.size(); ++d) {
     const rt::DrawCall& dc = sc->scene.drawcalls[d];
     const rt::States& st = dc.states;
+    if (d >= sc->first_tail_dc) {
+      for (uint32_t i = 0; i < dc.prim_count; ++i) sc->tail_prims.push_back((int32_t)(dc.prim_offset + i));
+      continue;
+    }
     if (st.blend_enabled || st.stencil_test || (st.color_writemask & 0xf) != 0xf)
       sc->unsupported = "drawcall " + std::to_string(d) + " uses blending/stencil/partial writes";
     if (st.depth_test) {
@@ -143,7 +183,17 @@ int rt_scene_load_range(const char* path, uint32_t start_draw, uint32_t end_draw
   std::reverse(sc->layers.begin(), sc->layers.end());
   sc->tie_high = geom_func == VX_OM_DEPTH_FUNC_LEQUAL;
   sc->build_tris = std::move(build);
+  // the fold addresses the tail's records by pid - first pid
+  for (size_t j = 1; j < sc->tail_prims.size(); ++j)
+    if (sc->tail_prims[j] != sc->tail_prims[0] + (int32_t)j) return fail("drawcalls' primitives are not consecutive");
   *out = sc.release();
+  return 0;
+}
+
+int rt_scene_om_split(rt_scene_h s, uint32_t* first_tail_drawcall, uint32_t* tail_prims) {
+  if (!s) return fail("null argument");
+  if (first_tail_drawcall) *first_tail_drawcall = s->first_tail_dc;
+  if (tail_prims) *tail_prims = (uint32_t)s->tail_prims.size();
   return 0;
 }
 
@@ -330,6 +380,8 @@ int rt_renderer_create(rt_scene_h s, const char* kernel_dir, rt_renderer_h* out)
         return fail("cannot upload kernel " + path);
     }
   }
+  // a scene with an ordered tail renders its plain and shadow frames with rt_om
+  if (!s->tail_prims.empty() && load_image(r.get(), "rt_om.vxbin", &r->krnl_om) != 0) return -1;
   rt_kernel_arg_t& a = r->arg;
   std::memset(&a, 0, sizeof(a));
   // 3 padding records: the kernel fetches all 4 slots of a leaf at once
@@ -494,6 +546,8 @@ int rt_renderer_export_records(rt_renderer_h r, uint32_t which, void* out, uint6
     case RT_REC_SLIST: b = a.slist_on ? r->slist : nullptr; n = (r->sl_entries + 1) * sizeof(rt_tri_t); break;
     case RT_REC_CDESC:
     case RT_REC_CDESC_HOST: b = r->cdesc_n ? r->cdesc : nullptr; n = (uint64_t)r->cdesc_n * sizeof(rt_cdesc_t); break;
+    case RT_REC_OIDX: b = a.otail_count ? r->oidx : nullptr; n = (uint64_t)r->local_tiles * 16 * 8; break;
+    case RT_REC_OLIST: b = a.otail_count ? r->olist : nullptr; n = (r->olist_entries + RT_OLIST_PAD) * 4; break;
     default: return fail("unknown record array");
   }
   if (!b) return fail("record array not present in this configuration");
@@ -559,6 +613,42 @@ int rt_scene_setup_vis(rt_scene_h s, uint32_t width, uint32_t height, uint32_t* 
       out[3 * g + 2] = v.zmin;
     }
   }
+  return 0;
+}
+
+// the ordered tail's per-resolution records, in tail order: covered-pixel
+// rectangles (app/vis.h) and, when asked for, the rt_vtri_t records
+static void tail_records(const rt_scene* s, uint32_t width, uint32_t height, std::vector<rt::VisPrim>* vis,
+                         std::vector<rt_vtri_t>* vtris) {
+  vis->clear();
+  if (vtris) vtris->clear();
+  for (size_t d = s->first_tail_dc; d < s->scene.drawcalls.size(); ++d) {
+    const rt::DrawCall& dc = s->scene.drawcalls[d];
+    for (uint32_t i = 0; i < dc.prim_count; ++i) {
+      const uint32_t g = dc.prim_offset + i;
+      rt_prim_t p;
+      rt_bbox_t bb{0, 0};
+      const bool ok = rt::PrimSetup(s->scene.prims[g], width, height, dc.viewport[4], dc.viewport[5], &p) ==
+                          rt::kSetupOk &&
+                      rt::PrimBBox(s->scene.prims[g], width, height, &bb) == rt::kSetupOk;
+      vis->push_back(rt::ComputeVisPrim(p, ok, bb, width, height));
+      if (vtris) vtris->push_back(rt::MakeVisTri(p, vis->back(), (int32_t)g));
+    }
+  }
+}
+
+int rt_scene_setup_olists(rt_scene_h s, uint32_t width, uint32_t height, uint32_t* idx, uint32_t* ent,
+                          uint64_t* entries, uint64_t* blocks) {
+  if (!s || width == 0 || height == 0) return fail("bad argument");
+  std::vector<rt::VisPrim> vis;
+  tail_records(s, width, height, &vis, nullptr);
+  const uint32_t tx = (width + 31u) >> RT_TILE_LOG, ty = (height + 31u) >> RT_TILE_LOG;
+  std::vector<uint32_t> ix, en;
+  rt::BuildTailLists(s->tail_prims, vis, tx, tx * ty, 0u, 1u, &ix, &en);
+  if (entries) *entries = en.size();
+  if (blocks) *blocks = ix.size() / 2;
+  if (idx && !ix.empty()) std::memcpy(idx, ix.data(), ix.size() * 4);
+  if (ent && !en.empty()) std::memcpy(ent, en.data(), en.size() * 4);
   return 0;
 }
 
@@ -778,6 +868,28 @@ static int build_block_lists(rt_renderer* r, const std::vector<rt::VisPrim>& vis
   return 0;
 }
 
+// The ordered tail's per-block lists and rt_vtri_t records of this
+// configuration (app/vis.h BuildTailLists), built here on the host -- a tail
+// holds at most a few hundred primitives -- and uploaded.
+static int build_tail_lists(rt_renderer* r) {
+  const rt_scene* s = r->sc;
+  rt_kernel_arg_t& a = r->arg;
+  std::vector<rt::VisPrim> vis;
+  std::vector<rt_vtri_t> vtris;
+  tail_records(s, a.width, a.height, &vis, &vtris);
+  std::vector<uint32_t> idx, ent;
+  rt::BuildTailLists(s->tail_prims, vis, a.tiles_x, r->local_tiles, a.shard_index, a.shard_count, &idx, &ent);
+  r->olist_entries = ent.size();
+  for (uint32_t i = 0; i < RT_OLIST_PAD; ++i) ent.push_back((uint32_t)s->tail_prims[0]);
+  if (upload(r->dev, idx.data(), idx.size() * 4, &r->oidx, &a.oidx_addr) ||
+      upload(r->dev, ent.data(), ent.size() * 4, &r->olist, &a.olist_addr) ||
+      upload(r->dev, vtris.data(), vtris.size() * sizeof(rt_vtri_t), &r->ovtris, &a.ovtris_addr))
+    return -1;
+  a.otail_base = (uint32_t)s->tail_prims[0];
+  a.otail_count = (uint32_t)s->tail_prims.size();
+  return 0;
+}
+
 // Tile layout, work order and kernel flags of a configuration; the
 // per-resolution records come from the device setup (device_setup.cpp,
 // kernels/rt_setup.hip; the default) or from the host loops below
@@ -872,6 +984,12 @@ int rt_renderer_configure(rt_renderer_h r, const rt_render_params_t* p) {
   const bool raster = (p->flags & RT_RENDER_RASTER) != 0;
   if (!raster && !r->sc->unsupported.empty())
     return fail("scene not supported by the RT path (use RT_RENDER_RASTER): " + r->sc->unsupported, -2);
+  // a scene with an ordered tail (RT_SCENE_OM_LAYERS): plain and shadow frames
+  // run rt_om (head traced, tail folded through the output merger)
+  const bool tail = !raster && !r->sc->tail_prims.empty();
+  if (tail && (p->flags & (RT_RENDER_PATH | RT_RENDER_FLAT | RT_RENDER_BVH_WALK | RT_RENDER_INSTRUMENTED)))
+    return fail("a scene with an ordered tail renders plain and shadow frames only (no RT_RENDER_PATH / FLAT / "
+                "BVH_WALK / INSTRUMENTED; or use RT_RENDER_RASTER)", -2);
   const bool compact = shards > 1 || (p->flags & RT_RENDER_COMPACT);
   if (raster && (compact || (p->flags & RT_RENDER_INSTRUMENTED)))
     return fail("RT_RENDER_RASTER renders whole frames, uninstrumented");
@@ -930,7 +1048,13 @@ int rt_renderer_configure(rt_renderer_h r, const rt_render_params_t* p) {
   // the regular RT / PT images walk only the binary16 BVH4 (RT_ONLY_BVH4H);
   // any other layout runs the generic images (the deep ones: every layout,
   // 32-entry stack)
-  if (!raster && !(p->flags & RT_RENDER_FLAT) && !(a.flags & RT_FLAG_BVH4H) && !r->deep &&
+  // (rt_om walks the binary16 BVH4 only, as packets whose one-VGPR stack holds
+  // RT_STACK_DEEP entries; it has no generic image: a head whose tree is
+  // another layout -- the layouts the deep images exist for -- is refused)
+  if (tail && s->geometry.size() > 0 && !(a.flags & RT_FLAG_BVH4H))
+    return fail("a scene with an ordered tail needs the binary16 BVH4; this tree needs the generic (deep) "
+                "images, which have no output-merger variant (use RT_RENDER_RASTER)", -2);
+  if (!raster && !tail && !(p->flags & RT_RENDER_FLAT) && !(a.flags & RT_FLAG_BVH4H) && !r->deep &&
       load_deep_images(r) != 0)
     return -1;
   // path tracing in two kernels (pt_primary, pt_queue: the compacted path
@@ -989,6 +1113,10 @@ int rt_renderer_configure(rt_renderer_h r, const rt_render_params_t* p) {
   } else if (host_setup(r, p, raster, order_on, lists, &heavy) != 0) {
     return -1;
   }
+  a.oidx_addr = a.olist_addr = a.ovtris_addr = 0;
+  a.otail_base = a.otail_count = 0;
+  r->olist_entries = 0;
+  if (tail && build_tail_lists(r) != 0) return -1;
   const double setup_ms = ms_since(t1);
   if (order_on) {
     // path tracing: tiles that geometry covers (first in the order;
@@ -1021,7 +1149,8 @@ int rt_renderer_configure(rt_renderer_h r, const rt_render_params_t* p) {
   // the whole-block tier's chunk descriptors (device setup, the RT images;
   // env RT_CHUNK_DESC=0: none, the kernels work the task map out themselves)
   const char* cde = std::getenv("RT_CHUNK_DESC");
-  if (device && !raster && !(p->flags & RT_RENDER_FLAT) && r->local_tiles > 0 && !(cde && std::atoi(cde) == 0) &&
+  // (rt_om works its task map out itself)
+  if (device && !raster && !tail && !(p->flags & RT_RENDER_FLAT) && r->local_tiles > 0 && !(cde && std::atoi(cde) == 0) &&
       rtapp::chunk_desc(r, &launches) != 0)
     return -1;
   uint64_t args_addr = 0;
@@ -1054,12 +1183,13 @@ int rt_renderer_configure(rt_renderer_h r, const rt_render_params_t* p) {
   // counter rows of two frames would mix), not compact / sharded (the gather
   // copies from the one pointer rt_framebuffer_device gave it), not the
   // two-kernel path tracer, not the raster pipeline (depth buffer, blending),
-  // not the RT_TILE_LIMIT probe (its frames leave pixels unwritten).
+  // not the RT_TILE_LIMIT probe (its frames leave pixels unwritten), not
+  // the frames of a scene with an ordered tail (ordinary frames on lane 0).
   r->lanes = false;
   r->lane_break = false;
   r->cur_buf = r->prev_buf = -1;
   r->cbuf1_off = 0;
-  if (r->set_lane && r->set_lane(r->dev, -1) == 0 && r->set_words && !raster && !compact && !r->pq && r->local_tiles > 0 &&
+  if (r->set_lane && r->set_lane(r->dev, -1) == 0 && r->set_words && !raster && !tail && !compact && !r->pq && r->local_tiles > 0 &&
       !(p->flags & (RT_RENDER_COUNTERS | RT_RENDER_INSTRUMENTED)) && !std::getenv("RT_TILE_LIMIT")) {
     uint64_t addr1 = 0;
     if (r->cbuf1 && r->cbuf1_bytes == r->cbuf_bytes) {
@@ -1156,6 +1286,8 @@ int render_start(rt_renderer_h r, bool sync) {
   const bool bvh = mode == 0 && (f & RT_RENDER_BVH_WALK) && !r->deep && (r->arg.flags & RT_FLAG_BVH4H) &&
                    r->krnl_bvh[k];
   vx_buffer_h img = bvh ? r->krnl_bvh[k] : r->krnl[mode][k];
+  // a scene with an ordered tail: head traced, tail folded, one launch
+  if (mode == 0 && !r->sc->tail_prims.empty()) img = r->krnl_om;
   return start(img) ? 0 : fail("vx_start failed");
 }
 }  // namespace

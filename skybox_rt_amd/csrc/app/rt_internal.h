@@ -24,6 +24,11 @@ struct rt_scene {
   std::vector<int32_t> layers;    // screen-layer prims, descending pid
   std::string unsupported;        // non-empty: the RT path cannot render it
   bool tie_high = false;
+  // RT_SCENE_OM_LAYERS: the ordered tail -- the first drawcall the RT path
+  // cannot trace and every drawcall after it; geometry / layers / build_tris /
+  // tie_high then describe the drawcalls before it (the traced head) only
+  uint32_t first_tail_dc = 0;       // = the drawcall count when there is no tail
+  std::vector<int32_t> tail_prims;  // the tail's prims in submission order (ascending, consecutive)
   double parse_ms = 0, bvh_ms = 0;
 };
 
@@ -65,6 +70,10 @@ struct rt_renderer {
   // rt_bvh / rt_bvh_stats, the packet walks without the list code paths
   vx_buffer_h krnl_bvh[2] = {};
   vx_buffer_h sah_krnl = nullptr;  // bvh_sah.vxbin, loaded by the first device build
+  // scenes with an ordered tail: rt_om.vxbin (plain and shadow frames), the
+  // per-block tail lists and the tail's rt_vtri_t records (host-built per configure)
+  vx_buffer_h krnl_om = nullptr, oidx = nullptr, olist = nullptr, ovtris = nullptr;
+  uint64_t olist_entries = 0;
   vx_buffer_h pathq = nullptr, pathq_ctr = nullptr;
   bool pq = false;          // the configuration runs the two-kernel path tracer
   vx_buffer_h nodes = nullptr, nodes4 = nullptr, tris = nullptr, layers = nullptr, dcs = nullptr, tex = nullptr;
@@ -155,7 +164,7 @@ struct rt_renderer {
                            &setup_krnl, &verts, &pdc, &dcz, &layer_list, &geometry_list, &vis,
                            &blist, &bidx, &cdesc, &sidx, &slist, &krnl_pq[0][0], &krnl_pq[0][1],
                            &krnl_pq[1][0], &krnl_pq[1][1], &pathq, &pathq_ctr,
-                           &krnl_bvh[0], &krnl_bvh[1], &sah_krnl};
+                           &krnl_bvh[0], &krnl_bvh[1], &sah_krnl, &krnl_om, &oidx, &olist, &ovtris};
     for (auto* b : bufs) {
       if (*b) vx_mem_free(*b);
       *b = nullptr;

@@ -125,6 +125,30 @@ rt_vtri_t MakeVisTri(const rt_prim_t& p, const VisPrim& v, int32_t pid) {
   return t;
 }
 
+void BuildTailLists(const std::vector<int32_t>& tail, const std::vector<VisPrim>& vis, uint32_t tiles_x,
+                    uint32_t local_tiles, uint32_t shard_index, uint32_t shard_count,
+                    std::vector<uint32_t>* idx, std::vector<uint32_t>* ent) {
+  const uint32_t nblk = local_tiles * 16u;
+  std::vector<std::vector<uint32_t>> lists(nblk);
+  for (size_t j = 0; j < tail.size(); ++j) {  // ascending pid: every list ascends
+    const VisPrim& v = vis[j];
+    if (!v.any) continue;
+    for (uint32_t by = (v.ry & 0xffffu) >> 3; by <= (v.ry >> 16) >> 3; ++by)
+      for (uint32_t bx = (v.rx & 0xffffu) >> 3; bx <= (v.rx >> 16) >> 3; ++bx) {
+        const uint32_t t = (by >> 2) * tiles_x + (bx >> 2);
+        if (t % shard_count != shard_index) continue;
+        lists[((t / shard_count) << 4) | ((by & 3u) << 2) | (bx & 3u)].push_back((uint32_t)tail[j]);
+      }
+  }
+  idx->clear();
+  ent->clear();
+  for (const auto& l : lists) {
+    idx->push_back((uint32_t)ent->size());
+    idx->push_back((uint32_t)l.size());
+    ent->insert(ent->end(), l.begin(), l.end());
+  }
+}
+
 namespace {
 
 struct Cover {

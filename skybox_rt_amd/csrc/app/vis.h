@@ -39,6 +39,19 @@ VisPrim ComputeVisPrim(const rt_prim_t& p, bool ok, const rt_bbox_t& bbox, uint3
 // the 64-B leaf / layer record of primitive `pid`
 rt_vtri_t MakeVisTri(const rt_prim_t& p, const VisPrim& v, int32_t pid);
 
+// Per-block lists of an ordered tail (rt_common.h oidx / olist; the fold of
+// kernels/rt_om_kernel.hip): for every local 8x8 block of the shard's tiles
+// -- block lt * 16 + (by & 3) * 4 + (bx & 3) of local tile lt = t / shards,
+// t % shards == shard_index, the per-block candidate lists' numbering -- the
+// tail primitives whose covered-pixel rectangle reaches the block, in
+// ascending primitive index (submission order: the output merger is order
+// dependent, so no depth ordering and no early out).  `tail`: the tail's pids,
+// ascending; `vis[j]`: the record of tail[j].  idx: first entry and count per
+// block; ent: the lists, concatenated (no padding).
+void BuildTailLists(const std::vector<int32_t>& tail, const std::vector<VisPrim>& vis, uint32_t tiles_x,
+                    uint32_t local_tiles, uint32_t shard_index, uint32_t shard_count,
+                    std::vector<uint32_t>* idx, std::vector<uint32_t>* ent);
+
 // rt_vnode_t for every node of a tree given by its child references (4 per
 // node; a BVH2 uses slots 0-1, RT_EMPTY_REF elsewhere; leaf references
 // index `leaf_pids`, the pid of every leaf triangle record in tris order).

@@ -13,6 +13,8 @@
 //   dcs     [num_dc]     rt_dcstate_t 64 B per-drawcall shading state
 //   ptris   [num_prims]  rt_tri_t    48 B  clip-space triangle by pid
 //   geom    [num_geom]   rt_tri_t    48 B  geometry triangles, ascending pid (flat)
+//   ovtris  [tail prims] rt_vtri_t   64 B  the ordered tail's primitives, ascending pid (rt_om)
+//   oidx / olist         u32              per-block lists of tail pids (rt_om)
 //   cbuf    W*H*4 (linear, row 0 = NDC y=-1) or tiles*1024*4 (compact shard)
 #pragma once
 
@@ -230,7 +232,17 @@ typedef struct {
   uint32_t cdesc_first;    // the first chunk of the whole-block tier (the chunks the table covers)
   uint64_t cdesc_addr;     // rt_cdesc_t per 64-task chunk of the whole-block tier, in work order
                            // (0: no table, the kernels work the task map out themselves)
+  // the ordered tail (rt_om_kernel.hip; vx_rt.h RT_SCENE_OM_LAYERS): the drawcalls the RT
+  // path cannot trace, folded over the traced head's pixels in submission order
+  uint64_t oidx_addr;      // uint32[2] per local 8x8 block (bidx's numbering): first entry, count
+  uint64_t olist_addr;     // u32 pid per entry, ascending per block (+ RT_OLIST_PAD padding entries)
+  uint64_t ovtris_addr;    // rt_vtri_t per tail primitive: record of pid at pid - otail_base
+  uint32_t otail_base;     // the first tail primitive (the tail's pids are consecutive)
+  uint32_t otail_count;    // tail primitives (0: no tail)
 } rt_kernel_arg_t;
+// padding entries after the last tail list (the first tail pid): the fold
+// loads the entry two ahead and the record one ahead of the one it tests
+#define RT_OLIST_PAD 2u
 // One 64-task chunk of the whole-block tier (an 8x8 pixel block), written by
 // the device setup (rt_setup.hip RTS_CDESC) and restated on the host
 // (app/setup.cpp ChunkDescs): everything rt_kernel's chunk_map / chunk_pixel

@@ -1522,6 +1522,32 @@ __device__ __forceinline__ int32_t block_primary(const Scene& S, uint2 oc, uint3
   }
   return act ? bpid : -1;
 }
+// block_primary that also gives the winner's 24-bit depth word (*bzo;
+// VX_OM_DEPTH_MASK, the cleared word, without a winner): the same scan, for
+// a kernel that goes on merging fragments over the pixel (rt_om_kernel.hip)
+__device__ __forceinline__ int32_t block_primary_z(const Scene& S, uint2 oc, uint32_t px, uint32_t py,
+                                                   bool act, bool tie_high, Counters& cnt, uint32_t* bzo) {
+  (void)cnt;
+  if (!act) px = 0xffffffffu;
+  const uint32_t pp = px > 0xffffu ? 0xffffffffu : px | (py << 16);
+  uint32_t bz = VX_OM_DEPTH_MASK;
+  int32_t bpid = -1;
+  uint4 e[2];
+  S.A.sld_u4n<2>(S.blist + 16u * oc.x, e);
+  for (uint32_t k = 0; k < oc.y; k += 2) {
+    if (__ballot(rect2_in(e[0].y, e[0].z, pp) && e[0].w <= bz) == 0) break;
+    uint4 r0[4], r1[4], en[2];
+    S.A.sld_u4n<4>(S.vgeom + 64u * e[0].x, r0);
+    S.A.sld_u4n<4>(S.vgeom + 64u * e[1].x, r1);
+    S.A.sld_u4n<2>(S.blist + 16u * (oc.x + k + 2), en);
+    vis_test(r0[0], r0[1], r0[2], r0[3], px, py, tie_high, bz, bpid);
+    if (k + 1 < oc.y) vis_test(r1[0], r1[1], r1[2], r1[3], px, py, tie_high, bz, bpid);
+    e[0] = en[0];
+    e[1] = en[1];
+  }
+  *bzo = act ? bz : VX_OM_DEPTH_MASK;
+  return act ? bpid : -1;
+}
 
 // primary visibility of the wave's pixels: the block's candidate list when
 // the host built lists (blist_blocks), else the packet walk of the tree

@@ -30,13 +30,15 @@ RT_RENDER_COMPACT = 0x200
 RT_RENDER_COUNTERS = 0x400
 RT_RENDER_HOST_SETUP = 0x800
 RT_RENDER_BVH_WALK = 0x2000
+RT_SCENE_OM_LAYERS = 0x1
 # rt_renderer_export_records arrays: name -> (id, dtype, words per record)
 RECORDS = {"prims": (0, np.int32, 32), "bbox": (1, np.uint32, 2), "vis": (2, np.uint32, 4),
            "vnodes": (3, np.uint32, 16), "vtris": (4, np.int32, 16), "vlayers": (5, np.int32, 16),
            "vgeom": (6, np.int32, 16), "order": (7, np.uint32, 1), "ptris": (8, np.float32, 12),
            "geom": (9, np.float32, 12), "bidx": (10, np.uint32, 2), "blist": (11, np.uint32, 4),
            "cdesc": (14, np.uint32, 4), "cdesc_host": (15, np.uint32, 4),
-           "sidx": (12, np.uint32, 2), "slist": (13, np.float32, 12)}
+           "sidx": (12, np.uint32, 2), "slist": (13, np.float32, 12),
+           "oidx": (16, np.uint32, 2), "olist": (17, np.uint32, 1)}
 RT_BVH_STACK4_UNUSED = 0xFFFFFFFF
 RT_BVH_BUILD_HOST = 2
 CLEAR_COLOR = 0xFF000000               # draw3d/main.cpp:47
@@ -106,6 +108,9 @@ def lib():
         vp, u32, u64 = C.c_void_p, C.c_uint32, C.c_uint64
         sig = {
             "rt_scene_load": [C.c_char_p, C.POINTER(vp)],
+            "rt_scene_load_ex": [C.c_char_p, u32, u32, u32, C.POINTER(vp)],
+            "rt_scene_om_split": [vp, C.POINTER(u32), C.POINTER(u32)],
+            "rt_scene_setup_olists": [vp, u32, u32, vp, vp, C.POINTER(u64), C.POINTER(u64)],
             "rt_scene_free": [vp],
             "rt_scene_info": [vp, C.POINTER(SceneInfo)],
             "rt_scene_export_prims": [vp, vp, u64],
@@ -166,10 +171,39 @@ class Scene:
         self._h = handle
 
     @classmethod
-    def load(cls, path: str) -> "Scene":
+    def load(cls, path: str, om_layers: bool = False) -> "Scene":
+        """om_layers=True (RT_SCENE_OM_LAYERS): a scene the RT path cannot
+        trace as a whole (blending, stencil, colour masks, layers after
+        geometry) is split at the first such drawcall; its plain and shadow
+        frames trace the drawcalls before it and fold the rest -- the ordered
+        tail -- over them through the output merger (kernels/rt_om_kernel.hip)."""
         h = C.c_void_p()
-        _check(lib().rt_scene_load(str(path).encode(), C.byref(h)), f"rt_scene_load({path})")
+        if om_layers:
+            _check(lib().rt_scene_load_ex(str(path).encode(), 0, 0xFFFFFFFF, RT_SCENE_OM_LAYERS,
+                                          C.byref(h)), f"rt_scene_load_ex({path})")
+        else:
+            _check(lib().rt_scene_load(str(path).encode(), C.byref(h)), f"rt_scene_load({path})")
         return cls(h)
+
+    def om_split(self):
+        """(first drawcall of the ordered tail, tail primitives); the drawcall
+        count and 0 when the tail is empty or the scene was loaded without om_layers."""
+        k, n = C.c_uint32(), C.c_uint32()
+        _check(lib().rt_scene_om_split(self._h, C.byref(k), C.byref(n)), "rt_scene_om_split")
+        return k.value, n.value
+
+    def setup_olists(self, width: int, height: int):
+        """The ordered tail's per-block lists at width x height (one shard):
+        (idx uint32[blocks, 2] = first entry, count per 8x8 block in bidx's
+        numbering; ent uint32[entries] = primitive indices, ascending per block)."""
+        ne, nb = C.c_uint64(), C.c_uint64()
+        _check(lib().rt_scene_setup_olists(self._h, width, height, None, None, C.byref(ne), C.byref(nb)),
+               "rt_scene_setup_olists")
+        idx = np.zeros((max(nb.value, 1), 2), np.uint32)
+        ent = np.zeros(max(ne.value, 1), np.uint32)
+        _check(lib().rt_scene_setup_olists(self._h, width, height, idx.ctypes.data, ent.ctypes.data,
+                                           C.byref(ne), C.byref(nb)), "rt_scene_setup_olists")
+        return idx[:nb.value], ent[:ne.value]
 
     def info(self) -> dict:
         i = SceneInfo()
@@ -321,7 +355,8 @@ class Renderer:
         """One per-resolution record array of the current configuration
         (RECORDS: prims, bbox, vis, vnodes, vtris, vlayers, vgeom, order,
         ptris, geom, bidx, blist -- the per-block candidate lists, blist with
-        its 3 padding entries), as [count, words]."""
+        its 3 padding entries; oidx, olist -- the ordered tail's per-block
+        lists, olist with its 2 padding entries), as [count, words]."""
         which, dt, words = RECORDS[name]
         n = C.c_uint64()
         _check(lib().rt_renderer_export_records(self._h, which, None, 0, C.byref(n)),
