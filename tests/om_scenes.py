@@ -152,6 +152,75 @@ def mutated_vase(directory, which: str) -> str:
     return out
 
 
+# ---- the layered synthetic scene, one tail state swept at a time ---------------
+# (tests/synth_scene.py make_layer_scene: an opaque LESS head and three tail
+# drawcalls with exact depth ties, nearer and farther fragments and 0 to 3+
+# layers of overdraw.)  State values are the trace's indices: compare 0 NEVER,
+# 1 LESS, 2 EQUAL, 3 LEQUAL, 4 GREATER, 5 NOTEQUAL, 6 GEQUAL, 7 ALWAYS; stencil
+# op 0 KEEP, 1 REPLACE, 2 INCR, 3 DECR, 4 ZERO, 5 INVERT; blend 0 ZERO, 1 ONE,
+# 2 SRC_RGB, 3 1-SRC_RGB, 4 SRC_A, 5 1-SRC_A, 6 DST_A, 7 1-DST_A, 8 DST_RGB,
+# 9 1-DST_RGB, 10 ALPHA_SAT.  The pass operation is the trace's stencil_zfail
+# (the draw3d quirk above).
+#
+# Tail drawcall 1 counts: LEQUAL without depth writes, stencil ALWAYS / DECR from
+# the cleared 0xff, alpha-blended -- it leaves stencil values 0xff, 0xfe, 0xfd,
+# ... and destination alphas other than 0xff for tail drawcall 2, the swept one.
+# Tail drawcall 3 reads back: drawcall 2's triangles again, depth test off,
+# blended where the stencil's low two bits are EQUAL 0xfe's (so 0xfe and INVERT's
+# 0x02 pass, 0xff, 0xfd, 0xfc, 0x00 and 0x01 fail), writing no stencil -- what
+# drawcall 2 left in the stencil plane shows in the colour plane, the only
+# plane the om_layers path exposes.
+LAYER_COUNTING = dict(depth_test=1, depth_func=3, depth_writemask=0, stencil_test=1, stencil_func=7,
+                      stencil_zpass=3, stencil_zfail=3, stencil_fail=0, stencil_ref=0,
+                      stencil_mask=0xFF, stencil_writemask=0xFF, blend_enabled=1, blend_src=4,
+                      blend_dst=5)
+LAYER_READER = dict(stencil_test=1, stencil_func=2, stencil_ref=0xFE, stencil_mask=0x03,
+                    stencil_writemask=0, blend_enabled=1, blend_src=4, blend_dst=5)
+LAYER_SWEPT = dict(depth_test=1, depth_func=3, depth_writemask=1, blend_enabled=1, blend_src=4,
+                   blend_dst=5, color_writemask=0xF)
+_STENCIL = dict(stencil_test=1, stencil_ref=0xFE, stencil_mask=0xFF, stencil_writemask=0xFF)
+# family -> (values, the swept drawcall's states for value v)
+LAYER_FAMILIES = {
+    "depth_func": (range(8), lambda v: dict(depth_func=v)),
+    "stencil_func": (range(8), lambda v: dict(_STENCIL, stencil_func=v, stencil_zpass=5,
+                                              stencil_zfail=5, stencil_fail=4)),
+    "pass_op": (range(6), lambda v: dict(_STENCIL, stencil_func=7, stencil_zpass=v, stencil_zfail=v,
+                                         stencil_fail=0)),
+    "fail_op": (range(6), lambda v: dict(_STENCIL, stencil_func=2, stencil_zpass=2, stencil_zfail=2,
+                                         stencil_fail=v)),
+    "blend_src": (range(11), lambda v: dict(blend_src=v)),
+    "blend_dst": (range(11), lambda v: dict(blend_dst=v)),
+    "color_writemask": (range(16), lambda v: dict(color_writemask=v)),
+}
+LAYER_CASES = [(f, v) for f, (values, _) in LAYER_FAMILIES.items() for v in values]
+
+
+def layer_scene(directory, family: str, value: int) -> str:
+    """Write the layered scene with `family` = value on its swept drawcall
+    into `directory`; the path."""
+    from synth_scene import make_layer_scene
+    out = os.path.join(str(directory), f"layers_{family}_{value}.cgltrace")
+    if not os.path.exists(out):
+        make_layer_scene(out, [LAYER_COUNTING, dict(LAYER_SWEPT, **LAYER_FAMILIES[family][1](value)),
+                               LAYER_READER])
+    return out
+
+
+# vase's own sweeps (a real scene): (family, drawcall, values)
+VASE_SWEEPS = (("blend_src", 4, range(11)), ("blend_dst", 4, range(11)), ("color_writemask", 3, range(16)))
+VASE_CASES = [(tag, dc, v) for tag, dc, values in VASE_SWEEPS for v in values]
+
+
+def swept_vase(directory, tag: str, drawcall: int, value: int) -> str:
+    out = os.path.join(str(directory), f"vase_{tag}_{drawcall}_{value}.cgltrace")
+    if not os.path.exists(out):
+        with gzip.open(scene_file("vase"), "rt") as f:
+            text = f.read()
+        with open(out, "w") as f:
+            f.write(rewrite_states(text, [(drawcall, tag, value)]))
+    return out
+
+
 # ---- GPU side ------------------------------------------------------------------
 def gpu_frame(path, width, height, shadows, counters=False, **kw):
     """One frame of `path` loaded with om_layers=True -> (framebuffer, stats)."""

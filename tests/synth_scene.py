@@ -5,6 +5,7 @@ cgltrace: boost_serialization v15); one depth-tested (LESS) drawcall of n
 random triangles in clip space, w in [90, 110] like tekkaman's model."""
 import gzip
 import os
+import re
 
 import numpy as np
 
@@ -14,11 +15,11 @@ _ITEM0 = ('<item class_id="6" tracking_level="0" version="0"><first>{i}</first>'
           '<second class_id="7" tracking_level="0" version="0">'
           '<pos class_id="8" tracking_level="0" version="0"><x>{x:.9e}</x><y>{y:.9e}</y>'
           '<z>{z:.9e}</z><w>{w:.9e}</w></pos><color><r>{r:.9e}</r><g>{g:.9e}</g><b>{b:.9e}</b>'
-          '<a>1.000000000e+00</a></color><texcoord class_id="9" tracking_level="0" version="0">'
+          '<a>{a:.9e}</a></color><texcoord class_id="9" tracking_level="0" version="0">'
           '<u>0.000000000e+00</u><v>0.000000000e+00</v></texcoord></second></item>')
 _ITEM = ('<item><first>{i}</first><second><pos><x>{x:.9e}</x><y>{y:.9e}</y><z>{z:.9e}</z>'
          '<w>{w:.9e}</w></pos><color><r>{r:.9e}</r><g>{g:.9e}</g><b>{b:.9e}</b>'
-         '<a>1.000000000e+00</a></color><texcoord><u>0.000000000e+00</u><v>0.000000000e+00</v>'
+         '<a>{a:.9e}</a></color><texcoord><u>0.000000000e+00</u><v>0.000000000e+00</v>'
          '</texcoord></second></item>')
 
 
@@ -56,7 +57,8 @@ def make_chain_scene(path: str, n: int, ratio: float = 1.6, base: float = 1e-3) 
     return _write(path, verts, np.full((n, 3), 0.5))
 
 
-def _write(path, verts, col):
+def _geometry_xml(verts, col, alpha: float = 1.0) -> str:
+    """the <vertices> and <primitives> elements of one drawcall"""
     n = len(col)
     items = []
     for t in range(n):
@@ -64,21 +66,105 @@ def _write(path, verts, col):
             x, y, z, ww = (float(a[t]) for a in verts[k])
             fmt = _ITEM0 if not items else _ITEM
             items.append(fmt.format(i=3 * t + k, x=x, y=y, z=z, w=ww, r=col[t, 0], g=col[t, 1],
-                                    b=col[t, 2]))
+                                    b=col[t, 2], a=alpha))
     prims = ['<item class_id="11" tracking_level="0" version="0"><i0>0</i0><i1>1</i1><i2>2</i2></item>']
     prims += [f"<item><i0>{3 * t}</i0><i1>{3 * t + 1}</i1><i2>{3 * t + 2}</i2></item>"
               for t in range(1, n)]
+    return (f'<vertices class_id="5" tracking_level="0" version="0"><count>{3 * n}</count>'
+            f'<bucket_count>{3 * n}</bucket_count><item_version>0</item_version>' + "".join(items) +
+            '</vertices><primitives class_id="10" tracking_level="0" version="0">'
+            f'<count>{n}</count><item_version>0</item_version>' + "".join(prims) + "</primitives>")
+
+
+def _write(path, verts, col):
     tmpl = open(scene_path("triangle")).read()
     head, rest = tmpl.split('<vertices class_id="5"', 1)
     head = head.replace("<depth_test>0</depth_test>", "<depth_test>1</depth_test>")
     head = head.replace("<depth_func>0</depth_func>", "<depth_func>1</depth_func>")
     head = head.replace("<depth_writemask>0</depth_writemask>", "<depth_writemask>1</depth_writemask>")
     tail = rest.split("</primitives>", 1)[1]
-    xml = (head + f'<vertices class_id="5" tracking_level="0" version="0"><count>{3 * n}</count>'
-           f'<bucket_count>{3 * n}</bucket_count><item_version>0</item_version>' + "".join(items) +
-           '</vertices><primitives class_id="10" tracking_level="0" version="0">'
-           f'<count>{n}</count><item_version>0</item_version>' + "".join(prims) + "</primitives>" + tail)
+    xml = head + _geometry_xml(verts, col) + tail
     os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
     with gzip.open(path, "wt") as f:
+        f.write(xml)
+    return path
+
+
+# ---- a small layered scene for the output-merger state sweeps ---------------
+# An opaque LESS head, then tail drawcalls whose states the caller chooses.
+# Tail drawcalls re-submit some of the head's (and each other's) triangles
+# vertex for vertex -- exact depth ties -- next to new triangles in front of
+# and behind what is there, so all three outcomes of a depth compare occur,
+# and overdraw runs from 0 to more than 3 layers across the frame.
+LAYER_HEAD_STATES = dict(depth_test=1, depth_func=1, depth_writemask=1)
+
+
+def _layer_tris(rng, n, size, depth_range):
+    """n triangles: (verts as in _write, colours [n, 3]); a corner's depth
+    z / w is uniform in depth_range, w is the triangle's (90..110)"""
+    w = rng.uniform(90.0, 110.0, n)
+    cx, cy = rng.uniform(-0.75, 0.75, n), rng.uniform(-0.75, 0.75, n)
+    verts = []
+    for _ in range(3):
+        ox, oy = rng.uniform(-size, size, n), rng.uniform(-size, size, n)
+        zn = rng.uniform(depth_range[0], depth_range[1], n)
+        verts.append(((cx + ox) * w, (cy + oy) * w, zn * w, w))
+    return verts, rng.uniform(0.15, 1.0, (n, 3))
+
+
+def _pick(tris, idx):
+    verts, col = tris
+    return [tuple(a[idx] for a in v) for v in verts], col[idx]
+
+
+def _join(*parts):
+    verts = [tuple(np.concatenate([p[0][k][c] for p in parts]) for c in range(4)) for k in range(3)]
+    return verts, np.concatenate([p[1] for p in parts])
+
+
+def layer_geometry(seed: int = 3):
+    """[head, tail 1, tail 2, tail 3] triangle sets of the layered scene;
+    tail 3 is tail 2 again, so a third drawcall can read back what the second
+    left in the depth/stencil plane"""
+    rng = np.random.default_rng(seed)
+    head = _layer_tris(rng, 20, 0.4, (0.35, 0.65))
+    near1, far1 = _layer_tris(rng, 6, 0.35, (0.1, 0.3)), _layer_tris(rng, 6, 0.35, (0.7, 0.9))
+    tail1 = _join(_pick(head, np.arange(0, 8)), near1, far1)
+    near2, far2 = _layer_tris(rng, 5, 0.35, (0.05, 0.45)), _layer_tris(rng, 5, 0.35, (0.55, 0.95))
+    tail2 = _join(_pick(head, np.arange(4, 14)), _pick(near1, np.arange(0, 3)),
+                  _pick(far1, np.arange(0, 3)), near2, far2)
+    return [head, tail1, tail2, tail2]
+
+
+def _drawcall_xml(template_item: str, states: dict, verts, col, alpha: float) -> str:
+    xml = template_item
+    for tag, value in states.items():
+        assert xml.count(f"<{tag}>") == 1, tag
+        head, rest = xml.split(f"<{tag}>", 1)
+        xml = head + f"<{tag}>{int(value)}" + rest[rest.index(f"</{tag}>"):]
+    head, rest = xml.split('<vertices class_id="5"', 1)
+    return head + _geometry_xml(verts, col, alpha) + rest.split("</primitives>", 1)[1]
+
+
+def make_layer_scene(path: str, tail_states, seed: int = 3, tail_alpha=(0.625, 0.375, 0.5)) -> str:
+    """Writes the layered scene (plain text) to `path` (returned): drawcall 0
+    is the opaque head (LAYER_HEAD_STATES), drawcall 1 + i carries
+    tail_states[i] (trace state tags -> values, on top of the template's
+    all-off states) and vertex alpha tail_alpha[i].  Three tail drawcalls."""
+    assert len(tail_states) == 3
+    tmpl = open(scene_path("triangle")).read()
+    start = tmpl.index('<item class_id="2"')
+    end = tmpl.index("</drawcalls>")
+    item = tmpl[start:end]
+    geo = layer_geometry(seed)
+    calls = [_drawcall_xml(item, LAYER_HEAD_STATES, *geo[0], 1.0)]
+    for st, g, a in zip(tail_states, geo[1:], tail_alpha):
+        # boost writes a class's attributes at its first occurrence only
+        calls.append(re.sub(r' class_id="\d+" tracking_level="\d+" version="\d+"', "",
+                            _drawcall_xml(item, st, *g, a)))
+    xml = (tmpl[:start].replace("<count>1</count>", f"<count>{len(calls)}</count>") + "".join(calls) +
+           tmpl[end:])
+    os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
+    with open(path, "w") as f:
         f.write(xml)
     return path
