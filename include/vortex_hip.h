@@ -115,6 +115,20 @@ typedef int (*vx_hip_set_launch_words_t)(vx_device_h hdevice, const uint32_t* wo
  * ordinary one and this call returns -1 for any lane -- how a caller learns
  * (with lane -1) whether launches can overlap before it sets up for them. */
 typedef int (*vx_hip_set_launch_lane_t)(vx_device_h hdevice, int lane);
+/* the grid, in workgroups, of the next vx_start (then the module's again; 0:
+ * the module's): a launch whose kernel deals fewer steps than the module's
+ * oversubscribed grid has waves (vx_spawn.h vx_spawn_steps_ex) starts only
+ * the workgroups that find work.  Never above the module's grid (the counter
+ * slab's rows, VX_HIP_BLOCKS_PER_CU): a larger request launches the module's
+ * grid.  Kernels deal their work by the grid they find, so any value renders
+ * the same frame.  vx_hip_last_run reports the grid launched. */
+typedef int (*vx_hip_set_launch_grid_t)(vx_device_h hdevice, uint32_t blocks);
+/* the launch shape of the kernel image at device address `krnl_addr` (an
+ * uploaded vxbin; loaded as a module now if no launch has done so): threads
+ * per workgroup and the module's grid in workgroups -- what a caller needs to
+ * turn a step count into vx_hip_set_launch_grid's blocks */
+typedef int (*vx_hip_image_launch_shape_t)(vx_device_h hdevice, uint64_t krnl_addr, uint32_t* block,
+                                           uint32_t* grid);
 
 #ifdef __cplusplus
 }

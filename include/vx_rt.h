@@ -292,6 +292,9 @@ typedef struct {
                              (0: the lists of an unchanged light were kept) */
   uint32_t slist_stale;   /* 1: the light moved since its lists were built and none are queued:
                              frames walk the BVH for their shadow rays (rt_renderer_set_list_policy) */
+  uint32_t lane_grid;     /* workgroups of a frame started on a launch lane (rt_render_start with
+                             frames overlapping): its waves take RT_LANE_CHUNKS (2) chunks each;
+                             0: the image's grid, as every frame rendered alone by rt_render */
 } rt_setup_stats_t;
 /* (reads back the status of shadow lists queued by rt_renderer_set_light:
  * waits for the device) */

@@ -349,6 +349,8 @@ int rt_renderer_create(rt_scene_h s, const char* kernel_dir, rt_renderer_h* out)
   r->set_tag = (vx_hip_set_launch_tag_t)vx_driver_symbol("vx_hip_set_launch_tag");
   r->set_words = (vx_hip_set_launch_words_t)vx_driver_symbol("vx_hip_set_launch_words");
   r->set_lane = (vx_hip_set_launch_lane_t)vx_driver_symbol("vx_hip_set_launch_lane");
+  r->set_grid = (vx_hip_set_launch_grid_t)vx_driver_symbol("vx_hip_set_launch_grid");
+  r->launch_shape = (vx_hip_image_launch_shape_t)vx_driver_symbol("vx_hip_image_launch_shape");
   r->host_mem = (vx_hip_host_mem_t)vx_driver_symbol("vx_hip_host_mem");
   if (r->host_mem) {
     void* h = nullptr;
@@ -494,12 +496,30 @@ int rt_renderer_export_vis_tree(rt_renderer_h r, int32_t* refs, uint32_t* num_no
   return 0;
 }
 
+// the grid of a frame on a launch lane (rt_internal.h lane_grid), from the image's workgroup
+// size and grid: the driver loads the image for the answer, as its first launch would
+static uint32_t lane_grid_of(rt_renderer* r) {
+  if (r->lane_grid_known) return r->lane_grid;
+  r->lane_grid_known = true;
+  r->lane_grid = 0;
+  uint64_t ia = 0;
+  uint32_t block = 0, mgrid = 0;
+  if (r->lane_chunks > 1 && r->krnl[0][0] && vx_mem_address(r->krnl[0][0], &ia) == 0 &&
+      r->launch_shape(r->dev, ia, &block, &mgrid) == 0 && block >= 64) {
+    const uint32_t chunks = (r->arg.num_tasks + 63u) / 64u, per = r->lane_chunks * (block / 64u);
+    const uint32_t g = std::max(1u, (chunks + per - 1u) / per);
+    if (g < mgrid) r->lane_grid = g;
+  }
+  return r->lane_grid;
+}
+
 int rt_renderer_setup_stats(rt_renderer_h r, rt_setup_stats_t* st) {
   if (!r || !st) return fail("null argument");
   if (!r->configured) return fail("renderer not configured");
   if (rtapp::settle_lists(r) != 0) return -1;
   r->setup.slist_on = r->arg.slist_on;
   r->setup.slist_stale = r->sl_stale ? 1u : 0u;
+  r->setup.lane_grid = lane_grid_of(r);
   *st = r->setup;
   return 0;
 }
@@ -1201,6 +1221,21 @@ int rt_renderer_configure(rt_renderer_h r, const rt_render_params_t* p) {
     r->cbuf1_off = (uint32_t)addr1 - (uint32_t)a.cbuf_addr;
     r->lanes = (r->cbuf1_off & ~RT_LW_CBUF_MASK) == 0;  // (the allocator's granule is 256 B)
   }
+  // Overlapped primary + shadow frames of the list image launch fewer waves: with two
+  // frames resident the chip stays full, the frame is bound by the passage of its waves
+  // through the wave slots, and a wave that takes RT_LANE_CHUNKS (default 2) chunks pays
+  // the per-wave prologue and exit once for them -- vx_spawn deals chunk c to wave c mod W
+  // for whatever grid it finds, so the frame is the same.  A frame rendered alone, and a
+  // frame kept off the lanes (behind a list rebuild), keeps the image's grid: there the
+  // longer waves only lengthen the frame's tail.
+  r->lane_grid = 0;
+  r->lane_chunks = 0;
+  r->lane_grid_known = false;
+  if (r->lanes && r->set_grid && r->launch_shape && !(p->flags & (RT_RENDER_PATH | RT_RENDER_FLAT)) && !bvh_walk) {
+    uint32_t per = 2;
+    if (const char* e = std::getenv("RT_LANE_CHUNKS")) per = std::min(64u, std::max(1u, (uint32_t)std::atoi(e)));
+    if (per > 1) r->lane_chunks = per;
+  }
   // the render arguments: one buffer for the renderer's life (its address,
   // the launches' STARTUP_ARG, stays put), rewritten in stream order behind
   // the setup just queued -- no wait for the device
@@ -1263,7 +1298,14 @@ int render_start(rt_renderer_h r, bool sync) {
   if (buf) lw[3] |= r->cbuf1_off & RT_LW_CBUF_MASK;
   auto start = [&](vx_buffer_h img) {
     if (r->set_words && r->set_words(r->dev, lw, 4) != 0) return false;
-    if (flip && !r->lane_break && r->set_lane(r->dev, buf) != 0) return false;
+    if (flip && !r->lane_break) {  // a frame on a launch lane, on the overlapped frames' grid
+      if (r->set_lane(r->dev, buf) != 0) return false;
+      // (not while the light-space lists are stale: those frames' shadow rays walk the BVH,
+      // their waves are long, and two chunks a wave measured slower there -- bench series
+      // moving_light 0.0184 -> 0.0192 ms)
+      const uint32_t g = r->sl_stale ? 0u : lane_grid_of(r);
+      if (g != 0 && r->set_grid(r->dev, g) != 0) return false;
+    }
     if (vx_start(r->dev, img, r->args) != 0) return false;
     r->lane_break = false;
     r->prev_buf = flip ? r->cur_buf : -1;  // (a frame into the buffer in use keeps no earlier one)

@@ -131,6 +131,17 @@ struct rt_renderer {
   // a cross-lane event each way
   bool lane_break = false;
   vx_hip_set_launch_lane_t set_lane = nullptr;
+  // the grid, in workgroups, of a frame that goes to a launch lane (0: the image's grid):
+  // overlapped frames keep the chip full, so their waves take two chunks each and half as
+  // many waves pay the per-wave prologue and exit; a frame rendered alone keeps a wave per
+  // chunk on the image's grid
+  // (worked out from the image's workgroup size by the first frame that needs it, or by
+  // rt_renderer_setup_stats: asking the driver loads the image, which a configure must not pay)
+  uint32_t lane_grid = 0;
+  uint32_t lane_chunks = 0;  // chunks per wave of such a frame; 0: the configuration has no lane grid
+  bool lane_grid_known = false;
+  vx_hip_set_launch_grid_t set_grid = nullptr;
+  vx_hip_image_launch_shape_t launch_shape = nullptr;
   rt_render_params_t params{};
   rt_kernel_arg_t arg{};
   bool configured = false;

@@ -435,7 +435,9 @@ __device__ __forceinline__ void flush(int slot, uint32_t v) { vx_mpm_add(RT_MPM_
 // 0.01084 ms vs 0.01108 at 16/CU; registers for 8 waves per SIMD, so all
 // 1 024 workgroups of 512 threads are resident at once (r05j)
 __device__ __attribute__((used)) uint32_t __vx_grid_per_cu = 4;
+#ifndef RT_WAVES_PER_EU  // (an A/B passing the macro keeps its value)
 #define RT_WAVES_PER_EU 8
+#endif
 #endif
 #ifdef RT_WAVES_PER_EU
 VX_MAIN_OCC(rt_kernel_arg_t, arg, RT_BLOCK_THREADS, RT_WAVES_PER_EU) {

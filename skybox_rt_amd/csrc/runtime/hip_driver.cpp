@@ -352,6 +352,8 @@ class vx_device {
     // words below only differ from the in-flight run's when another image
     // or argument block is started, which the constant upload check catches
     const int want_lane = launch_lane_;  // vx_hip_set_launch_lane: this start() only
+    const uint32_t want_grid = launch_grid_;  // vx_hip_set_launch_grid: this start() only
+    launch_grid_ = 0;
     launch_lane_ = -1;
     if (depth_ <= 1) wait_idle();
     dcr_set(VX_DCR_BASE_STARTUP_ADDR0, (uint32_t)(krnl_addr & 0xffffffffu));
@@ -364,6 +366,8 @@ class vx_device {
     dcr_set(VX_DCR_HIP_MPM_ROWS, rows ? 1u : 0u);
     Module* m = nullptr;
     if (load_module(krnl_addr, &m) != 0) return -1;
+    // the launch's grid: the module's, or the smaller one asked for
+    const uint32_t grid = want_grid != 0 && want_grid < m->grid ? want_grid : m->grid;
     // constant blocks are only re-sent when they changed since this module's
     // last launch (a steady-state frame loop issues memset + launch only)
     const bool upload = !m->base_set || !m->dcrs_set ||
@@ -437,7 +441,7 @@ class vx_device {
       group_mods_.clear();
       ++runs_issued_;
     }
-    group_mods_.push_back({m, m->grid, rows});
+    group_mods_.push_back({m, grid, rows});
     const bool timed = group_timed_ && !tail;
     timed_[slot] = (timed || tail) && last;  // the run completes (and is timed) with its last launch
     tail_[slot] = tail;
@@ -449,7 +453,7 @@ class vx_device {
       group_untimed_ = false;
     }
     if (tail) {
-      HIP_CHECK(hipExtModuleLaunchKernel(m->entry, m->grid * m->block, 1, 1, m->block, 1, 1, 0,
+      HIP_CHECK(hipExtModuleLaunchKernel(m->entry, grid * m->block, 1, 1, m->block, 1, 1, 0,
                                          ls, kparams, nullptr, nullptr, nullptr, 0));
       const uint32_t nonce = ++tail_nonce_;
       tail_nonce_slot_[slot] = nonce;
@@ -460,21 +464,21 @@ class vx_device {
       void* dparams[2] = {&hp, &nv};
       HIP_CHECK(hipModuleLaunchKernel(m->done, 1, 1, 1, 64, 1, 1, 0, ls, dparams, nullptr));
     } else if (!timed) {
-      HIP_CHECK(hipExtModuleLaunchKernel(m->entry, m->grid * m->block, 1, 1, m->block, 1, 1, 0,
+      HIP_CHECK(hipExtModuleLaunchKernel(m->entry, grid * m->block, 1, 1, m->block, 1, 1, 0,
                                          ls, kparams, nullptr, nullptr, nullptr, 0));
     } else if (launch_mode_ == 2) {
-      HIP_CHECK(hipExtModuleLaunchKernel(m->entry, m->grid * m->block, 1, 1, m->block, 1, 1, 0,
+      HIP_CHECK(hipExtModuleLaunchKernel(m->entry, grid * m->block, 1, 1, m->block, 1, 1, 0,
                                          ls, kparams, nullptr, nullptr, nullptr, 0));
     } else if (launch_mode_ == 1) {
       // the dispatch packet itself carries the start/stop timestamps: no
       // separate event packets between back-to-back frames
-      HIP_CHECK(hipExtModuleLaunchKernel(m->entry, m->grid * m->block, 1, 1, m->block, 1, 1, 0,
+      HIP_CHECK(hipExtModuleLaunchKernel(m->entry, grid * m->block, 1, 1, m->block, 1, 1, 0,
                                          ls, kparams, nullptr,
                                          first ? ev_start_[slot] : nullptr,
                                          last ? ev_stop_[slot] : nullptr, 0));
     } else {
       if (first) HIP_CHECK(hipEventRecord(ev_start_[slot], ls));
-      HIP_CHECK(hipModuleLaunchKernel(m->entry, m->grid, 1, 1, m->block, 1, 1, 0, ls,
+      HIP_CHECK(hipModuleLaunchKernel(m->entry, grid, 1, 1, m->block, 1, 1, 0, ls,
                                       kparams, nullptr));
       if (last) HIP_CHECK(hipEventRecord(ev_stop_[slot], ls));
     }
@@ -482,7 +486,7 @@ class vx_device {
     mpm_dirty_ = true;  // read back lazily by mpm_query (after wait_idle)
     last_rows_ = rows;
     last_module_ = m;
-    last_grid_ = m->grid;
+    last_grid_ = grid;
     last_block_ = m->block;
     return 0;
   }
@@ -697,6 +701,15 @@ class vx_device {
     return 0;
   }
   void set_launch_tag(uint32_t tag) { launch_tag_ = tag; }  // the next start()'s kernel argument
+  void set_launch_grid(uint32_t blocks) { launch_grid_ = blocks; }  // and its grid (0: the module's)
+  // threads per workgroup and the grid of the image at krnl_addr (loaded now if it was not)
+  int image_launch_shape(uint64_t krnl_addr, uint32_t* block, uint32_t* grid) {
+    Module* m = nullptr;
+    if (load_module(krnl_addr, &m) != 0) return -1;
+    if (block) *block = m->block;
+    if (grid) *grid = m->grid;
+    return 0;
+  }
   void set_launch_words(const uint32_t* w, uint32_t n) {       // and its launch words
     std::memset(launch_words_, 0, sizeof(launch_words_));
     std::memcpy(launch_words_, w, n * sizeof(uint32_t));
@@ -875,6 +888,7 @@ class vx_device {
   uint64_t stage_next_ = 0;
   uint32_t launch_tag_ = 0;
   uint32_t launch_words_[4] = {};
+  uint32_t launch_grid_ = 0;
   std::map<uint64_t, uint64_t> image_key_;  // image address -> module key
   hipStream_t stream_ = nullptr;  // lane 0
   // launch lanes (lanes.h): the second stream, one join event per lane waited
@@ -1107,6 +1121,18 @@ __attribute__((visibility("default"))) int vx_hip_set_launch_tag(vx_device_h hde
   ((vx_device*)hdevice)->set_launch_tag(tag);
   return 0;
 }
+__attribute__((visibility("default"))) int vx_hip_set_launch_grid(vx_device_h hdevice, uint32_t blocks) {
+  if (!hdevice) return -1;
+  ((vx_device*)hdevice)->set_launch_grid(blocks);
+  return 0;
+}
+
+__attribute__((visibility("default"))) int vx_hip_image_launch_shape(vx_device_h hdevice, uint64_t krnl_addr,
+                                                                     uint32_t* block, uint32_t* grid) {
+  if (!hdevice) return -1;
+  return ((vx_device*)hdevice)->image_launch_shape(krnl_addr, block, grid);
+}
+
 __attribute__((visibility("default"))) int vx_hip_set_launch_lane(vx_device_h hdevice, int lane) {
   if (hdevice == nullptr) return -1;
   return ((vx_device*)hdevice)->set_launch_lane(lane);
