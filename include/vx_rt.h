@@ -187,6 +187,58 @@ int rt_renderer_configure(rt_renderer_h r, const rt_render_params_t* params);
 int rt_render_start(rt_renderer_h r);
 int rt_render_wait(rt_renderer_h r);
 int rt_render(rt_renderer_h r);  /* start + wait */
+
+/* Progressive path tracing: samples per pixel accumulated on the device.
+ * NO REFERENCE (the reference has no path tracer, SURVEY.md 8(a) row A7;
+ * none of the entry points below has a counterpart there).
+ *
+ * Sample i of a renderer configured with seed s0 is the RT_RENDER_PATH pixel
+ * of seed (s0 + i) mod 2^32 as rt_render stores it (8 bits per channel; a
+ * pixel that starts no path: its primary colour).  One 16-byte record per
+ * framebuffer pixel, uint32 {sumR, sumG, sumB, n} at the pixel's framebuffer
+ * index (the compact / sharded layout included): the per-channel sums of the
+ * sample values and the number of samples in them.  An accumulation launch
+ * of k samples (image pt_accum.vxbin) resolves primary visibility, layers
+ * and shading once, reads each record, traces samples n .. n + k - 1, writes
+ * the record back with n + k and stores alpha | mean(R) << 16 | mean(G) << 8
+ * | mean(B) to the framebuffer in use, mean(c) = (2 * sum_c + n) / (2 * n) in
+ * integer division (rt_accum_resolve) -- so n is the sample cursor, nothing
+ * reaches the kernel between launches and launches queue back to back.  The
+ * first launch after accum_begin, accum_reset or rt_renderer_set_light (a
+ * moved light changes the integrand) treats every record as zero without
+ * reading it: no clearing launch, no copy.  With RT_RENDER_COUNTERS a
+ * launch's primary_rays / geometry_hits count once, shadow_rays / occluded /
+ * bounce_rays are the sums over its k samples.
+ *
+ * Accumulation launches are ordinary launches (no lane, the image's grid):
+ * they run behind overlapped frames in flight on both lanes.  Plain
+ * rt_render_start / rt_render frames in between behave as ever and leave the
+ * records alone.  rt_renderer_configure ends accumulation and frees the
+ * records. */
+/* on a configured RT_RENDER_PATH frame: allocate W*H*16 B (compact: local
+ * tiles * 1024 * 16 B); the next launch resets.  -2 (rt_last_error): not a
+ * path frame, RT_RENDER_INSTRUMENTED, the two-kernel queue form (env
+ * RT_PT_QUEUE=1), a kernel directory with its own pt_kernel.vxbin and no
+ * pt_accum.vxbin (pt_compact), a tree the generic (deep) images run.
+ * RT_RENDER_COUNTERS, BVH_WALK, COMPACT, HOST_SETUP and shards accumulate.
+ * NO REFERENCE. */
+int rt_renderer_accum_begin(rt_renderer_h r);
+/* the next launch resets; queues nothing.  NO REFERENCE. */
+int rt_renderer_accum_reset(rt_renderer_h r);
+/* one launch of `samples` (1..32) samples per pixel, no host wait; -2 for
+ * samples out of range, before accum_begin, or when the launch would take n
+ * past 2^24 (below that the u32 sums cannot overflow).  NO REFERENCE. */
+int rt_render_accumulate_start(rt_renderer_h r, uint32_t samples);
+int rt_render_accumulate(rt_renderer_h r, uint32_t samples);  /* start + wait.  NO REFERENCE. */
+/* samples queued since the last reset (the records' n once the launches ran).  NO REFERENCE. */
+int rt_renderer_accum_samples(rt_renderer_h r, uint32_t* n);
+/* the records, uint32[count][4] in framebuffer order (waits for the device).  NO REFERENCE. */
+int rt_read_accum(rt_renderer_h r, uint32_t* out, uint64_t count);
+/* the host restatement of the resolve: alpha_argb's alpha over the rounded
+ * means of rec = {sumR, sumG, sumB, n} (n = 0: alpha alone; a mean is clamped
+ * to 255, which sums of 8-bit samples never exceed).  NO REFERENCE. */
+uint32_t rt_accum_resolve(const uint32_t rec[4], uint32_t alpha_argb);
+
 int rt_render_stats(rt_renderer_h r, rt_stats_t* stats);
 /* HIP-event duration of the last launch only (no counter read-back) */
 int rt_render_kernel_ms(rt_renderer_h r, double* kernel_ms);

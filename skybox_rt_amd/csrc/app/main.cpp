@@ -22,7 +22,9 @@
 // build, -H host-loop setup, -O load the scene with RT_SCENE_OM_LAYERS (a
 // scene the RT path cannot trace as a whole renders on the RT path all the
 // same: its head traced, its ordered tail folded through the output merger,
-// vx_rt.h); multi-GPU (one process per GPU over
+// vx_rt.h); -A samples, with -P: that many samples per pixel accumulated on
+// the device (rt_render_accumulate: launches of 32, then one for the rest)
+// and their mean written, -r comparing as usual; multi-GPU (one process per GPU over
 // librt_shard.so / RCCL): -G rank,ranks -I idfile -- this process renders
 // 32x32 tiles t with t % ranks == rank, rank 0 writes the RCCL communicator
 // id to `idfile` (the others wait for it), every frame ends with
@@ -68,6 +70,7 @@ const char* id_file = "rt_shard.id";  // -I
 const char* build = nullptr;          // -B lbvh|sah: build the BVH on the device
 bool host_setup = false;              // -H: per-resolution records by the host loops
 bool om_layers = false;               // -O: RT_SCENE_OM_LAYERS
+uint32_t accum_samples = 0;           // -A: with -P, accumulate this many samples per pixel
 
 #ifdef RT_APP_RASTER
 const char* kOpts = "t:i:o:r:w:h:k:n:z?";
@@ -77,7 +80,7 @@ void usage() {
               "[-k tilelogsize] [-n repeat]\n");
 }
 #else
-const char* kOpts = "t:s:e:i:o:r:w:h:k:n:L:P:G:I:B:uxyzSRFHO?";
+const char* kOpts = "t:s:e:i:o:r:w:h:k:n:L:P:G:I:B:A:uxyzSRFHO?";
 void usage() {
   std::printf("Vortex 3D Rendering Test (MI355X).\n"
               "Usage: [-t trace] [-s startdraw] [-e enddraw] [-o output] [-r reference] [-w width] "
@@ -85,6 +88,8 @@ void usage() {
               "       [-S shadows] [-L x,y,w] [-n repeat] [-R raster | -P bounces | -F flat] "
               "[-G rank,ranks [-I idfile]] [-B lbvh|sah device BVH build] [-H host setup]\n"
               "       [-O trace the head, fold blended / stencil / masked drawcalls (RT_SCENE_OM_LAYERS)]\n"
+              "       [-A samples: with -P, accumulate that many samples per pixel on the device and "
+              "write their mean]\n"
               "       env RT_KERNEL_DIR: kernel images; RT_ASSETS_PATHS: search directories\n");
 }
 #endif
@@ -125,6 +130,7 @@ int main(int argc, char** argv) {
     case 'B': build = optarg; break;
     case 'H': host_setup = true; break;
     case 'O': om_layers = true; break;
+    case 'A': accum_samples = (uint32_t)std::atoi(optarg); break;
 #endif
     case '?': usage(); return 0;
     default: usage(); return -1;  // -i: in the reference's option string, never handled
@@ -145,6 +151,10 @@ int main(int argc, char** argv) {
     }
     std::printf("Tile log size %d: rendering through the draw3d raster pipeline\n", tile_log);
     raster = true;
+  }
+  if (accum_samples && (bounces < 0 || rank >= 0)) {
+    std::printf("Error: -A samples needs -P bounces (path tracing), one rank\n");
+    return 1;
   }
   const bool sharded = rank >= 0;
   if (sharded && (ranks < 1 || rank >= ranks || raster)) {
@@ -245,7 +255,31 @@ int main(int argc, char** argv) {
   rt_stats_t st;
   std::vector<uint32_t> gathered;
   if (sharded && rank == 0) gathered.resize((size_t)width * height);
-  for (uint32_t i = 0; i < repeat; ++i) {
+  if (accum_samples) {
+    // progressive path tracing: launches of 32 samples, then one for the rest;
+    // the framebuffer holds the mean of all of them
+    RT_CHECK(rt_renderer_accum_begin(r));
+    rt_stats_t sum;
+    std::memset(&sum, 0, sizeof(sum));
+    uint32_t launches = 0;
+    for (uint32_t left = accum_samples; left > 0; ++launches) {
+      const uint32_t k = left < 32u ? left : 32u;
+      RT_CHECK(rt_render_accumulate(r, k));
+      RT_CHECK(rt_render_stats(r, &st));
+      total += st.kernel_ms;
+      sum.shadow_rays += st.shadow_rays;
+      sum.bounce_rays += st.bounce_rays;
+      sum.occluded += st.occluded;
+      left -= k;
+    }
+    st.shadow_rays = sum.shadow_rays;
+    st.bounce_rays = sum.bounce_rays;
+    st.occluded = sum.occluded;
+    std::printf("Accumulated %u samples per pixel in %u launches, %.4f ms in all\n", accum_samples, launches,
+                total);
+    repeat = 1;  // the line below: the time of all launches, the rays of all samples
+  }
+  for (uint32_t i = 0; !accum_samples && i < repeat; ++i) {
     RT_CHECK(rt_render(r));
     RT_CHECK(rt_render_stats(r, &st));
     total += st.kernel_ms;

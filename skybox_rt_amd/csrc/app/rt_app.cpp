@@ -532,6 +532,12 @@ int rt_renderer_set_light(rt_renderer_h r, const float light[3]) {
   uint32_t launches = 0;
   if (rtapp::set_light(r, light, &launches) != 0) return -1;
   r->setup.slist_built = r->sl_mode ? 1u : 0u;
+  // a moved light changes what the accumulated samples estimate: the next
+  // accumulation launch starts the records over
+  if (r->accum_on) {
+    r->accum_reset = true;
+    r->accum_n = 0;
+  }
   return 0;
 }
 
@@ -1020,6 +1026,16 @@ int rt_renderer_configure(rt_renderer_h r, const rt_render_params_t* p) {
   r->params.shard_count = shards;
   for (vx_buffer_h* b : {&r->gather_recv, &r->gather_image})  // sized per configuration
     if (*b) { vx_mem_free(*b); *b = nullptr; }
+  // a configure ends accumulation (rt_renderer_accum_begin): the records go, once the
+  // launches still writing them have run
+  if (r->accum) {
+    if (vx_ready_wait(r->dev, VX_MAX_TIMEOUT) != 0) return fail("vx_ready_wait failed");
+    vx_mem_free(r->accum);
+    r->accum = nullptr;
+  }
+  r->accum_on = r->accum_reset = false;
+  r->accum_bytes = 0;
+  r->accum_n = 0;
   rt_kernel_arg_t& a = r->arg;
   a.width = p->width;
   a.height = p->height;
@@ -1239,7 +1255,8 @@ int rt_renderer_configure(rt_renderer_h r, const rt_render_params_t* p) {
   // the render arguments: one buffer for the renderer's life (its address,
   // the launches' STARTUP_ARG, stays put), rewritten in stream order behind
   // the setup just queued -- no wait for the device
-  if (!r->args && upload(r->dev, nullptr, sizeof(a), &r->args, &args_addr)) return -1;
+  // (behind the block, the accumulating path tracer's area: rt_renderer_accum_begin writes it)
+  if (!r->args && upload(r->dev, nullptr, sizeof(a) + sizeof(rt_accum_arg_t), &r->args, &args_addr)) return -1;
   if (r->copy_async ? r->copy_async(r->args, &a, 0, sizeof(a)) != 0
                     : vx_copy_to_dev(r->args, &a, 0, sizeof(a)) != 0)
     return fail("render argument upload failed");
@@ -1262,7 +1279,7 @@ int rt_renderer_set_list_policy(rt_renderer_h r, uint32_t defer_frames) {
 }
 
 namespace {
-int render_start(rt_renderer_h r, bool sync);
+int render_start(rt_renderer_h r, bool sync, uint32_t accum_k = 0);
 }
 
 int rt_render_start(rt_renderer_h r) { return render_start(r, false); }
@@ -1271,7 +1288,10 @@ namespace {
 // sync: the frame of rt_render (start + wait) -- an ordinary launch into the
 // buffer in use: the synchronous path neither flips the framebuffer nor asks
 // for a lane, it is the path of the rounds before
-int render_start(rt_renderer_h r, bool sync) {
+// accum_k > 0: an accumulation launch of that many samples (rt_render_accumulate_start) --
+// pt_accum instead of the frame's image, as such an ordinary launch (sync is set): behind the
+// overlapped frames in flight on both lanes by the driver's ordering of ordinary operations
+int render_start(rt_renderer_h r, bool sync, uint32_t accum_k) {
   if (!r || !r->configured) return fail("renderer not configured");
   // the moving light: the lists of a light that stayed for sl_defer frames
   // are queued before this frame (the frames before walked the BVH)
@@ -1296,6 +1316,8 @@ int render_start(rt_renderer_h r, bool sync) {
   const bool flip = r->lanes && !sync;
   const int buf = r->cur_buf < 0 ? 0 : flip ? r->cur_buf ^ 1 : r->cur_buf;
   if (buf) lw[3] |= r->cbuf1_off & RT_LW_CBUF_MASK;
+  if (accum_k)
+    lw[3] |= ((accum_k - 1u) << RT_LW_ACCUM_K_SHIFT) | (r->accum_reset ? RT_LW_ACCUM_RESET : 0u);
   auto start = [&](vx_buffer_h img) {
     if (r->set_words && r->set_words(r->dev, lw, 4) != 0) return false;
     if (flip && !r->lane_break) {  // a frame on a launch lane, on the overlapped frames' grid
@@ -1316,6 +1338,7 @@ int render_start(rt_renderer_h r, bool sync) {
   if (r->set_counters &&
       r->set_counters(r->dev, (f & (RT_RENDER_COUNTERS | RT_RENDER_INSTRUMENTED)) ? 1 : 0) != 0)
     return fail("vx_hip_set_counters failed");
+  if (accum_k) return start(r->krnl_accum) ? 0 : fail("vx_start failed");
   // a frame of the two-kernel path tracer is one launch group of 2
   if (mode == 1 && r->pq) {
     if (r->launch_group(r->dev, 2) != 0) return fail("vx_hip_launch_group failed");
@@ -1342,6 +1365,107 @@ int rt_render_wait(rt_renderer_h r) {
 int rt_render(rt_renderer_h r) {
   int e = render_start(r, true);
   return e ? e : rt_render_wait(r);
+}
+
+// ---- progressive accumulation (vx_rt.h; NO REFERENCE) ---------------------
+
+int rt_renderer_accum_begin(rt_renderer_h r) {
+  if (!r || !r->configured) return fail("renderer not configured");
+  const uint32_t f = r->params.flags;
+  if (!(f & RT_RENDER_PATH)) return fail("rt_renderer_accum_begin: not an RT_RENDER_PATH configuration", -2);
+  if (f & RT_RENDER_INSTRUMENTED)
+    return fail("rt_renderer_accum_begin: no instrumented accumulation image (RT_RENDER_INSTRUMENTED)", -2);
+  if (r->pq) return fail("rt_renderer_accum_begin: the two-kernel path queue (RT_PT_QUEUE=1) does not accumulate", -2);
+  // (a scene without geometry starts no path and walks no tree: any image serves it)
+  if (r->arg.num_geom > 0 && (r->deep || !(r->arg.flags & RT_FLAG_BVH4H)))
+    return fail("rt_renderer_accum_begin: pt_accum walks the binary16 BVH4 only; this tree runs the generic "
+                "(deep) images", -2);
+  if (!r->set_words) return fail("rt_renderer_accum_begin: the driver passes no launch words", -2);
+  if (!r->krnl_accum) {
+    // next to the pt_kernel.vxbin in use: the kernel directory's when it holds one (a
+    // directory with a path tracer of its own and no pt_accum, e.g. pt_compact, is refused)
+    std::string dir = r->kdir;
+    if (FILE* fk = std::fopen((dir + "/pt_kernel.vxbin").c_str(), "rb")) std::fclose(fk);
+    else dir = lib_dir();
+    const std::string path = dir + "/pt_accum.vxbin";
+    if (FILE* fa = std::fopen(path.c_str(), "rb")) std::fclose(fa);
+    else return fail("rt_renderer_accum_begin: no pt_accum.vxbin next to " + dir + "/pt_kernel.vxbin", -2);
+    if (vx_upload_kernel_file(r->dev, path.c_str(), &r->krnl_accum) != 0) {
+      r->krnl_accum = nullptr;
+      return fail("cannot upload kernel " + path);
+    }
+  }
+  const uint64_t bytes = r->cbuf_bytes * 4;  // 16 B per framebuffer pixel
+  if (!r->accum || r->accum_bytes != bytes) {
+    // (upload frees the old buffer: not under launches still writing it)
+    if (r->accum && vx_ready_wait(r->dev, VX_MAX_TIMEOUT) != 0) return fail("vx_ready_wait failed");
+    uint64_t addr = 0;
+    r->accum_on = false;
+    r->accum_bytes = 0;
+    if (upload(r->dev, nullptr, bytes, &r->accum, &addr)) return -1;
+    r->accum_bytes = bytes;
+    rt_accum_arg_t aa{};
+    aa.accum_addr = addr;
+    // behind the launches in flight, ahead of every launch started after it
+    if (r->copy_async ? r->copy_async(r->args, &aa, sizeof(rt_kernel_arg_t), sizeof(aa)) != 0
+                      : vx_copy_to_dev(r->args, &aa, sizeof(rt_kernel_arg_t), sizeof(aa)) != 0)
+      return fail("accumulation argument upload failed");
+  }
+  r->accum_on = true;
+  r->accum_reset = true;  // the records are not cleared: the first launch does not read them
+  r->accum_n = 0;
+  return 0;
+}
+
+int rt_renderer_accum_reset(rt_renderer_h r) {
+  if (!r || !r->configured) return fail("renderer not configured");
+  if (!r->accum_on) return fail("rt_renderer_accum_reset: no accumulation begun (rt_renderer_accum_begin)", -2);
+  r->accum_reset = true;
+  r->accum_n = 0;
+  return 0;
+}
+
+int rt_render_accumulate_start(rt_renderer_h r, uint32_t samples) {
+  if (!r || !r->configured) return fail("renderer not configured");
+  if (!r->accum_on) return fail("rt_render_accumulate: no accumulation begun (rt_renderer_accum_begin)", -2);
+  if (samples < 1 || samples > RT_ACCUM_MAX_K) return fail("rt_render_accumulate: samples must be in [1, 32]", -2);
+  if ((uint64_t)r->accum_n + samples > RT_ACCUM_MAX_SAMPLES)
+    return fail("rt_render_accumulate: more than 2^24 samples per pixel (the records' u32 sums)", -2);
+  const int e = render_start(r, true, samples);
+  if (e) return e;
+  r->accum_n += samples;
+  r->accum_reset = false;
+  return 0;
+}
+
+int rt_render_accumulate(rt_renderer_h r, uint32_t samples) {
+  int e = rt_render_accumulate_start(r, samples);
+  return e ? e : rt_render_wait(r);
+}
+
+int rt_renderer_accum_samples(rt_renderer_h r, uint32_t* n) {
+  if (!r || !n) return fail("null argument");
+  if (!r->configured || !r->accum_on) return fail("rt_renderer_accum_samples: no accumulation begun", -2);
+  *n = r->accum_n;
+  return 0;
+}
+
+int rt_read_accum(rt_renderer_h r, uint32_t* out, uint64_t count) {
+  if (!r || !out || !r->configured) return fail("renderer not configured");
+  if (!r->accum_on) return fail("rt_read_accum: no accumulation begun (rt_renderer_accum_begin)", -2);
+  if (count * 16 < r->accum_bytes) return fail("buffer too small");
+  return vx_copy_from_dev(out, r->accum, 0, r->accum_bytes) == 0 ? 0 : fail("vx_copy_from_dev failed");
+}
+
+uint32_t rt_accum_resolve(const uint32_t rec[4], uint32_t alpha_argb) {
+  const uint64_t n = rec[3];
+  if (n == 0) return alpha_argb & 0xff000000u;
+  uint32_t c = alpha_argb & 0xff000000u;
+  for (int k = 0; k < 3; ++k) {
+    const uint64_t m = (2 * (uint64_t)rec[k] + n) / (2 * n);  // round half up
+    c |= (uint32_t)(m > 255 ? 255 : m) << (16 - 8 * k);
+  }
+  return c;
 }
 
 int rt_render_stats(rt_renderer_h r, rt_stats_t* st) {

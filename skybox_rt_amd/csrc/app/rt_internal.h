@@ -76,6 +76,15 @@ struct rt_renderer {
   uint64_t olist_entries = 0;
   vx_buffer_h pathq = nullptr, pathq_ctr = nullptr;
   bool pq = false;          // the configuration runs the two-kernel path tracer
+  // progressive accumulation (vx_rt.h rt_renderer_accum_begin): pt_accum.vxbin, loaded by the
+  // first accum_begin from the directory pt_kernel.vxbin came from; the record buffer
+  // (rt_common.h rt_accum_arg_t: 16 B per framebuffer pixel) of the current configuration,
+  // named in the argument buffer behind rt_kernel_arg_t
+  vx_buffer_h krnl_accum = nullptr, accum = nullptr;
+  uint64_t accum_bytes = 0;
+  bool accum_on = false;     // between accum_begin and the next configure
+  bool accum_reset = false;  // the next accumulation launch carries RT_LW_ACCUM_RESET
+  uint32_t accum_n = 0;      // samples queued since the last reset: the records' n once they ran
   vx_buffer_h nodes = nullptr, nodes4 = nullptr, tris = nullptr, layers = nullptr, dcs = nullptr, tex = nullptr;
   vx_buffer_h ptris = nullptr, geom = nullptr, oms = nullptr, bbox = nullptr, zbuf = nullptr;
   vx_buffer_h order = nullptr;
@@ -175,7 +184,8 @@ struct rt_renderer {
                            &setup_krnl, &verts, &pdc, &dcz, &layer_list, &geometry_list, &vis,
                            &blist, &bidx, &cdesc, &sidx, &slist, &krnl_pq[0][0], &krnl_pq[0][1],
                            &krnl_pq[1][0], &krnl_pq[1][1], &pathq, &pathq_ctr,
-                           &krnl_bvh[0], &krnl_bvh[1], &sah_krnl, &krnl_om, &oidx, &olist, &ovtris};
+                           &krnl_bvh[0], &krnl_bvh[1], &sah_krnl, &krnl_om, &oidx, &olist, &ovtris,
+                           &krnl_accum, &accum};
     for (auto* b : bufs) {
       if (*b) vx_mem_free(*b);
       *b = nullptr;

@@ -208,7 +208,16 @@ struct PathState {
   int32_t pid;
   float t;
   float o[3], d[3], T[3], L[3];
+#ifdef PT_ACCUM
+  uint32_t seed;  // this sample's RNG seed (arg seed + the record's sample cursor + j)
+#endif
 };
+// the bounce RNG's seed: the configured one, or (image pt_accum) the sample's
+#ifdef PT_ACCUM
+#define PT_SEED(S, st) ((st).seed)
+#else
+#define PT_SEED(S, st) ((S).seed)
+#endif
 // (the pair form carrying the vertex normal from the hit instead of loading
 // the triangle again at the next vertex measured no gain, r05)
 
@@ -313,7 +322,7 @@ __device__ __forceinline__ bool path_step(const Scene& S, int32_t* stack, PathSt
   Ray b;
   if (alive) {
     b.o[0] = P[0]; b.o[1] = P[1]; b.o[2] = P[2];
-    bounce_dir(nrm, pt_key(S.seed, (st.xy >> 16) * S.width + (st.xy & 0xffffu), v), b.d);  // keyed by pixel
+    bounce_dir(nrm, pt_key(PT_SEED(S, st), (st.xy >> 16) * S.width + (st.xy & 0xffffu), v), b.d);  // keyed by pixel
     ray_setup(b);
     cnt.bounce += one;
     np = CO == 1 ? trace_coop(S, b, st.pid, tie_high, &nt, stack, hi, cnt)
@@ -359,7 +368,7 @@ __device__ __forceinline__ bool path_step_pair(const Scene& S, int32_t* stack, P
   Ray b;
   b.o[0] = P[0]; b.o[1] = P[1]; b.o[2] = P[2];
   if (alive) {
-    bounce_dir(nrm, pt_key(S.seed, (st.xy >> 16) * S.width + (st.xy & 0xffffu), v), b.d);  // keyed by pixel
+    bounce_dir(nrm, pt_key(PT_SEED(S, st), (st.xy >> 16) * S.width + (st.xy & 0xffffu), v), b.d);  // keyed by pixel
   } else {
     b.d[0] = 1.0f; b.d[1] = 1.0f; b.d[2] = 1.0f;
   }
@@ -548,6 +557,141 @@ __device__ __forceinline__ void queued_path(const vx_task_t& task, const Scene& 
 
 #else  // PT_MODE == 1
 
+#ifdef PT_ACCUM
+// ---- progressive accumulation (image pt_accum) -------------
+// A launch traces k samples of every path (launch word 3, RT_LW_ACCUM_*) on
+// top of one primary pass: sample j of a pixel whose record holds n samples
+// is the path of seed arg.seed + n + j.  The record -- uint32 {sumR, sumG,
+// sumB, n} at the pixel's framebuffer index, in the buffer rt_accum_arg_t
+// names behind the argument block -- is read once (not at all by a reset
+// launch), the 8-bit sample values are summed in registers, the record is
+// written once and the framebuffer gets the rounded mean.
+__device__ __forceinline__ uint32_t accum_buf(const Scene& S) {
+  uint64_t p = S.argp + sizeof(rt_kernel_arg_t);
+  asm volatile("" : "+s"(p));  // opaque, as task_args: read where used
+  const __attribute__((address_space(4))) rt_accum_arg_t* a =
+      (const __attribute__((address_space(4))) rt_accum_arg_t*)p;
+  return (uint32_t)a->accum_addr;
+}
+__device__ __forceinline__ uint4 accum_load(const Scene& S, uint32_t abuf, uint32_t out) {
+  if (S.lw3 & RT_LW_ACCUM_RESET) return make_uint4(0u, 0u, 0u, 0u);
+  return S.A.ld_u4(abuf + 16u * out);
+}
+// round-half-up mean (2 * sum + n) / (2 * n), as (sum + n / 2) / n: the same
+// quotient (for odd n the dropped half cannot carry), within 32 bits for
+// n <= 2^24 samples of at most 255
+__device__ __forceinline__ uint32_t accum_mean(uint32_t sum, uint32_t n) { return (sum + (n >> 1)) / n; }
+__device__ __forceinline__ void accum_store(const Scene& S, uint32_t abuf, uint32_t out, const uint4& rec,
+                                            uint32_t alpha) {
+  S.A.st_u4(abuf + 16u * out, rec);
+  store_out(S, out,
+            alpha | (accum_mean(rec.x, rec.w) << 16) | (accum_mean(rec.y, rec.w) << 8) | accum_mean(rec.z, rec.w));
+}
+// the saved primary state -> the path's first vertex, for the sample of `seed`
+// (the primary ray is formed again from the pixel: the same operations)
+__device__ __forceinline__ void accum_restart(const Scene& S, PathState& st, uint32_t color, int32_t hit,
+                                              float th, uint32_t seed) {
+  const float k255 = 1.0f / 255.0f;
+  Ray r;
+  primary_dir(S, st.xy & 0xffffu, st.xy >> 16, r);
+  st.pid = hit;
+  st.t = th;
+  st.seed = seed;
+  st.T[0] = (float)((color >> 16) & 0xffu) * k255;
+  st.T[1] = (float)((color >> 8) & 0xffu) * k255;
+  st.T[2] = (float)(color & 0xffu) * k255;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    st.o[k] = r.o[k];
+    st.d[k] = r.d[k];
+    st.L[k] = 0.0f;
+  }
+}
+__device__ __forceinline__ void accum_add(uint4& rec, const PathState& st) {
+  rec.x += to8(st.L[0]);
+  rec.y += to8(st.L[1]);
+  rec.z += to8(st.L[2]);
+}
+// lane_path's tail: the launch's samples of this lane's pixel, in the wave's
+// vertex-loop form (lane_path's comments)
+__device__ __forceinline__ void accum_path(const Scene& S, int32_t* stack, Counters& cnt, uint32_t xy,
+                                           uint32_t out, uint32_t color, int32_t hit, float th, bool in,
+                                           bool path, bool pair, bool coop) {
+  const uint32_t ns = ((S.lw3 & RT_LW_ACCUM_K_MASK) >> RT_LW_ACCUM_K_SHIFT) + 1u;
+  const uint32_t abuf = accum_buf(S);
+  if (in && !path) {  // no path starts here: every sample is the primary colour
+    uint4 rec = accum_load(S, abuf, out);
+    rec.x += ns * ((color >> 16) & 0xffu);
+    rec.y += ns * ((color >> 8) & 0xffu);
+    rec.z += ns * (color & 0xffu);
+    rec.w += ns;
+    S.A.st_u4(abuf + 16u * out, rec);
+    store_out(S, out, color);
+  }
+  if (!path && !pair && !coop) return;
+  PathState st;
+  st.task = 0;
+  st.xy = xy;
+  st.out = out;
+  st.alpha = color & 0xff000000u;
+  if (pair) {
+    // every lane stays in the loop until the wave's last sample ends (helpers
+    // trace their owner's shadow ray)
+    uint4 rec = make_uint4(0u, 0u, 0u, 0u);
+    if (path) rec = accum_load(S, abuf, out);
+    for (uint32_t j = 0; j < ns; ++j) {
+      accum_restart(S, st, color, hit, th, S.seed + rec.w + j);
+      bool act = path;
+      for (uint32_t v = 0; __ballot(act) != 0; ++v) act = path_step_pair(S, stack, st, v, act, cnt);
+      if (path) accum_add(rec, st);
+    }
+    if (path) {
+      rec.w += ns;
+      accum_store(S, abuf, out, rec, st.alpha);
+    }
+    return;
+  }
+  if (coop) {
+    // lanes 2p, 2p + 1 take pixel p's path (lane p) -- handed its primary
+    // state once; both trace every sample, lane 2p owns the record and the store
+    const bool hi = (lane_id() & 1u) != 0u;
+    const int src = (int)(lane_id() >> 1);
+    const bool pact = __shfl((int)path, src) != 0;
+    const bool own = pact && !hi;
+    st.xy = (uint32_t)__shfl((int)st.xy, src);
+    st.out = (uint32_t)__shfl((int)st.out, src);
+    color = (uint32_t)__shfl((int)color, src);
+    hit = __shfl(hit, src);
+    th = __shfl(th, src);
+    st.alpha = color & 0xff000000u;
+    int32_t* pstack = hi ? stack - 1 : stack;  // the pair's stack: lane 2p's column
+    if (!pact) return;
+    // (both lanes read the record: its n is the pair's sample cursor)
+    uint4 rec = accum_load(S, abuf, st.out);
+    for (uint32_t j = 0; j < ns; ++j) {
+      accum_restart(S, st, color, hit, th, S.seed + rec.w + j);
+      bool act = true;
+      for (uint32_t v = 0; act; ++v) act = path_step<1>(S, pstack, st, v, act, cnt, hi ? 1u : 0u);
+      accum_add(rec, st);
+    }
+    if (own) {
+      rec.w += ns;
+      accum_store(S, abuf, st.out, rec, st.alpha);
+    }
+    return;
+  }
+  uint4 rec = accum_load(S, abuf, out);
+  for (uint32_t j = 0; j < ns; ++j) {
+    accum_restart(S, st, color, hit, th, S.seed + rec.w + j);
+    for (uint32_t v = 0; path_step<0>(S, stack, st, v, true, cnt); ++v) {
+    }
+    accum_add(rec, st);
+  }
+  rec.w += ns;
+  accum_store(S, abuf, out, rec, st.alpha);
+}
+#endif  // PT_ACCUM
+
 // one pixel's whole path on its own lane (no compaction)
 __device__ __forceinline__ void lane_path(const vx_task_t& task, const Scene& S, int32_t* stack,
                                           Counters& cnt) {
@@ -577,6 +721,9 @@ __device__ __forceinline__ void lane_path(const vx_task_t& task, const Scene& S,
   primary_dir(S, x, y, r);
   const float th = hit >= 0 ? plane_t(S, r, hit) : 0.0f;
   const bool path = hit >= 0 && secondary_ok(th);  // a path starts at the winner's plane
+#ifdef PT_ACCUM
+  accum_path(S, stack, cnt, x | (y << 16), out, color, hit, th, in, path, pair, coop);
+#else
   if (!path && in) store_out(S, out, color);
   if (!path && !pair && !coop) return;
   const float k255 = 1.0f / 255.0f;
@@ -631,6 +778,7 @@ __device__ __forceinline__ void lane_path(const vx_task_t& task, const Scene& S,
   for (uint32_t v = 0; path_step<0>(S, stack, st, v, true, cnt); ++v) {
   }
   store_path_pixel(S, st);
+#endif  // PT_ACCUM
 }
 #endif
 

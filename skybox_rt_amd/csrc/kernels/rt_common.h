@@ -68,6 +68,14 @@
 // two launch lanes write apart.  In the launch word: rt_kernel_arg_t stays as it was;
 // added at the framebuffer stores (rt_trace.h store_out)
 #define RT_LW_CBUF_MASK 0xffffff00u
+// w[3] bits 2-7, read by the accumulating path tracer only (pt_kernel.hip PT_ACCUM, image
+// pt_accum): bit 2 = the launch treats every accumulation record as zero and does not read
+// it, bits 3-7 = the launch's samples per pixel minus one (1..32)
+#define RT_LW_ACCUM_RESET   0x4u
+#define RT_LW_ACCUM_K_SHIFT 3
+#define RT_LW_ACCUM_K_MASK  0xf8u
+#define RT_ACCUM_MAX_K      32u
+#define RT_ACCUM_MAX_SAMPLES (1u << 24)  // a record's u32 sums of 8-bit samples cannot overflow below it
 
 #define RT_DC_DEPTH   0x1u
 #define RT_DC_COLOR   0x2u
@@ -240,6 +248,14 @@ typedef struct {
   uint32_t otail_base;     // the first tail primitive (the tail's pids are consecutive)
   uint32_t otail_count;    // tail primitives (0: no tail)
 } rt_kernel_arg_t;
+// The accumulating path tracer's argument area, in the argument buffer right behind
+// rt_kernel_arg_t (which stays as it is): the accumulation buffer, one 16-B record
+// uint32 {sumR, sumG, sumB, n} per framebuffer pixel at the pixel's framebuffer index --
+// the per-channel sums of the 8-bit sample values and the number of samples in them
+typedef struct {
+  uint64_t accum_addr;
+  uint64_t pad;
+} rt_accum_arg_t;
 // padding entries after the last tail list (the first tail pid): the fold
 // loads the entry two ahead and the record one ahead of the one it tests
 #define RT_OLIST_PAD 2u

@@ -150,11 +150,19 @@ def lib():
             "rt_renderer_set_light": [vp, C.POINTER(C.c_float)],
             "rt_renderer_set_list_policy": [vp, u32],
             "rt_renderer_export_records": [vp, u32, vp, u64, C.POINTER(u64)],
+            "rt_renderer_accum_begin": [vp],
+            "rt_renderer_accum_reset": [vp],
+            "rt_render_accumulate_start": [vp, u32],
+            "rt_render_accumulate": [vp, u32],
+            "rt_renderer_accum_samples": [vp, C.POINTER(u32)],
+            "rt_read_accum": [vp, vp, u64],
         }
         for name, argtypes in sig.items():
             fn = getattr(h, name)
             fn.argtypes = argtypes
             fn.restype = C.c_int
+        h.rt_accum_resolve.argtypes = [C.POINTER(u32), u32]
+        h.rt_accum_resolve.restype = u32
         h.rt_last_error.restype = C.c_char_p
         h.rt_last_error.argtypes = []
         _h = h
@@ -441,6 +449,48 @@ class Renderer:
     def wait(self) -> None:
         _check(lib().rt_render_wait(self._h), "rt_render_wait")
 
+    # progressive path tracing (vx_rt.h rt_renderer_accum_begin; image pt_accum)
+    def accum_begin(self) -> None:
+        """Start accumulating samples per pixel on the configured path frame:
+        one uint32 {sumR, sumG, sumB, n} record per framebuffer pixel on the
+        device; the next accumulate() starts from zero.  configure() ends it."""
+        _check(lib().rt_renderer_accum_begin(self._h), "rt_renderer_accum_begin")
+
+    def accum_reset(self) -> None:
+        """The next accumulate() starts the records over (a flag of that
+        launch: nothing is queued).  set_light() does the same."""
+        _check(lib().rt_renderer_accum_reset(self._h), "rt_renderer_accum_reset")
+
+    def accumulate(self, samples: int, wait: bool = True) -> None:
+        """One launch tracing `samples` (1..32) more samples of every pixel --
+        sample i is the path frame of seed + i -- into the records; the
+        framebuffer gets the rounded mean of all samples so far.
+        wait=False: queued only (wait() later)."""
+        if wait:
+            _check(lib().rt_render_accumulate(self._h, int(samples)), "rt_render_accumulate")
+        else:
+            _check(lib().rt_render_accumulate_start(self._h, int(samples)), "rt_render_accumulate_start")
+
+    def accum_samples(self) -> int:
+        """Samples per pixel queued since the last reset."""
+        n = C.c_uint32()
+        _check(lib().rt_renderer_accum_samples(self._h, C.byref(n)), "rt_renderer_accum_samples")
+        return n.value
+
+    def accum(self) -> np.ndarray:
+        """The records: uint32 [H, W, 4] = sumR, sumG, sumB, n (compact /
+        sharded frames: the flat [local_tiles * 1024, 4] array in the compact
+        framebuffer's order)."""
+        p = self.params
+        if p.shard_count > 1 or p.flags & RT_RENDER_COMPACT:
+            n = self.stats()["local_tiles"] * TILE * TILE
+            out = np.zeros((max(n, 1), 4), np.uint32)
+            _check(lib().rt_read_accum(self._h, out.ctypes.data, n), "rt_read_accum")
+            return out[:n]
+        out = np.zeros((p.height, p.width, 4), np.uint32)
+        _check(lib().rt_read_accum(self._h, out.ctypes.data, p.height * p.width), "rt_read_accum")
+        return out
+
     def stats(self) -> dict:
         s = Stats()
         _check(lib().rt_render_stats(self._h, C.byref(s)), "rt_render_stats")
@@ -538,6 +588,13 @@ class Renderer:
             self.close()
         except Exception:
             pass
+
+
+def accum_resolve(rec, alpha_argb: int) -> int:
+    """rt_accum_resolve: the pixel an accumulation record {sumR, sumG, sumB, n}
+    resolves to -- alpha_argb's alpha over the rounded means (2 * sum + n) // (2 * n)."""
+    arr = (C.c_uint32 * 4)(*[int(v) for v in rec])
+    return int(lib().rt_accum_resolve(arr, int(alpha_argb) & 0xFFFFFFFF))
 
 
 def deinterleave_tiles(shards, width: int, height: int) -> np.ndarray:
