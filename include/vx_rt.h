@@ -347,6 +347,12 @@ typedef struct {
   uint32_t lane_grid;     /* workgroups of a frame started on a launch lane (rt_render_start with
                              frames overlapping): its waves take RT_LANE_CHUNKS (2) chunks each;
                              0: the image's grid, as every frame rendered alone by rt_render */
+  uint32_t bg_first_chunk; /* the background tier: the first chunk of the work order behind the
+                             tiles geometry reaches (16 * heavy_tiles); 0: the configuration is
+                             never tiered */
+  uint32_t tier_groups;   /* the geometry tier's workgroups (the launch tag) of a frame started
+                             on a launch lane -- with env RT_BG_TIER=2 of a frame rendered alone
+                             -- now; 0: that frame is untiered */
 } rt_setup_stats_t;
 /* (reads back the status of shadow lists queued by rt_renderer_set_light:
  * waits for the device) */

@@ -306,6 +306,41 @@ __device__ __forceinline__ int vx_spawn_tasks_ex(uint32_t num_tasks, F kernel_fu
   return vx_spawn_threads_ex(1u, &num_tasks, (const uint32_t*)nullptr, kernel_func, epilogue, arg);
 }
 
+/* Chunk-range form of vx_spawn_tasks_ex, for a launch whose waves are dealt
+ * in tiers (each tier a range of the launch's chunks and a set of its
+ * waves): this wave is wave `w` of the `nw` waves that share the chunks
+ * [c0, c1) of the launch's `num_tasks` tasks (c1 is clamped to the launch's
+ * chunk count), and takes chunks c0 + w, c0 + w + nw, ... below c1.  The
+ * launch still declares its whole task count; every chunk must lie in exactly
+ * one tier's range and every tier's waves must call this (or run the chunks
+ * themselves), which is the caller's business.  With c0 = 0, c1 = every chunk
+ * and the grid's waves it is vx_spawn_tasks_ex. */
+template <typename F, typename E, typename Arg>
+__device__ __forceinline__ int vx_spawn_chunks_ex(uint32_t num_tasks, uint32_t c0, uint32_t c1,
+                                                  uint32_t w, uint32_t nw, F kernel_func, E epilogue,
+                                                  Arg* arg) {
+  __vx_declare_tasks(num_tasks);
+  const uint32_t nchunks = (num_tasks + VX_CHUNK - 1) / VX_CHUNK;
+  if (c1 > nchunks) c1 = nchunks;
+  uint32_t ran = 0;
+  vx_task_t task;
+  task.threadIdx.x = task.threadIdx.y = task.threadIdx.z = 0;
+  task.blockIdx.y = task.blockIdx.z = 0;
+  for (uint32_t c = c0 + w; c < c1; c += nw) {
+    const uint32_t t = c * VX_CHUNK + (threadIdx.x & 63u);
+    if (t < num_tasks) {
+      task.task_id = t;
+      task.blockIdx.x = t;
+      kernel_func(task, arg);
+      ++ran;
+    }
+    epilogue(false, arg);
+  }
+  epilogue(true, arg);
+  vx_mpm_add(VX_MPM_TASKS, ran);
+  return 0;
+}
+
 /* Block-synchronous form for kernels that cooperate across the waves of a
  * workgroup (e.g. compaction queues in LDS): the block takes blockDim.x
  * consecutive tasks per step (wave w: tasks step*blockDim + 64w ..+63, the

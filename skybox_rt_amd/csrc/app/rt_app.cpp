@@ -22,6 +22,7 @@
 
 #include "VX_types.h"
 #include "app_util.h"
+#include "bg_tier.h"
 #include "bvh.h"
 #include "bvh_common.h"
 #include "cgltrace.h"
@@ -513,6 +514,26 @@ static uint32_t lane_grid_of(rt_renderer* r) {
   return r->lane_grid;
 }
 
+// the geometry tier's workgroups (the launch tag, runtime/bg_tier.h) of a primary + shadow frame
+// of image rt_kernel (k = 0) / rt_kernel_stats (k = 1) launched on `grid` workgroups (0: the
+// image's grid); 0: untiered.  `laned`: the frame goes to a launch lane.
+static uint32_t tier_groups_of(rt_renderer* r, int k, uint32_t grid, bool laned) {
+  if (!r->bg_ok || r->bg_mode == 0 || (r->bg_mode == 1 && !laned)) return 0;
+  if (r->sl_stale && !r->bg_stale) return 0;
+  if (!r->img_shape_known[k]) {
+    r->img_shape_known[k] = true;
+    uint64_t ia = 0;
+    if (!(r->launch_shape && r->krnl[0][k] && vx_mem_address(r->krnl[0][k], &ia) == 0 &&
+          r->launch_shape(r->dev, ia, &r->img_block[k], &r->img_grid[k]) == 0))
+      r->img_block[k] = r->img_grid[k] = 0;
+  }
+  if (r->img_block[k] < 64 || r->img_grid[k] == 0) return 0;
+  if (grid == 0 || grid > r->img_grid[k]) grid = r->img_grid[k];
+  const uint32_t chunks = (r->arg.num_tasks + 63u) / 64u;
+  return vxtier::tier_groups(vxtier::Config{}, chunks, r->bg_first / vxtier::kChunksPerTile, grid,
+                             r->img_block[k] / 64u, r->bg_cost);
+}
+
 int rt_renderer_setup_stats(rt_renderer_h r, rt_setup_stats_t* st) {
   if (!r || !st) return fail("null argument");
   if (!r->configured) return fail("renderer not configured");
@@ -520,6 +541,12 @@ int rt_renderer_setup_stats(rt_renderer_h r, rt_setup_stats_t* st) {
   r->setup.slist_on = r->arg.slist_on;
   r->setup.slist_stale = r->sl_stale ? 1u : 0u;
   r->setup.lane_grid = lane_grid_of(r);
+  r->setup.bg_first_chunk = r->bg_ok ? r->bg_first : 0u;
+  {
+    const int k = (r->params.flags & RT_RENDER_INSTRUMENTED) ? 1 : 0;
+    r->setup.tier_groups = r->lanes ? tier_groups_of(r, k, r->sl_stale ? 0u : lane_grid_of(r), true)
+                                    : tier_groups_of(r, k, 0u, false);
+  }
   *st = r->setup;
   return 0;
 }
@@ -1256,10 +1283,43 @@ int rt_renderer_configure(rt_renderer_h r, const rt_render_params_t* p) {
   // the launches' STARTUP_ARG, stays put), rewritten in stream order behind
   // the setup just queued -- no wait for the device
   // (behind the block, the accumulating path tracer's area: rt_renderer_accum_begin writes it)
-  if (!r->args && upload(r->dev, nullptr, sizeof(a) + sizeof(rt_accum_arg_t), &r->args, &args_addr)) return -1;
+  // (and behind that the background tier's: rt_tier_arg_t, constant until the next configure)
+  if (!r->args &&
+      upload(r->dev, nullptr, RT_TIER_ARG_OFFSET + sizeof(rt_tier_arg_t), &r->args, &args_addr))
+    return -1;
   if (r->copy_async ? r->copy_async(r->args, &a, 0, sizeof(a)) != 0
                     : vx_copy_to_dev(r->args, &a, 0, sizeof(a)) != 0)
     return fail("render argument upload failed");
+  // The background tier: primary + shadow frames of the list image with the chunk table over
+  // every chunk, not compact / sharded / path (runtime/bg_tier.h eligible; neither the generic
+  // image nor the ordered-tail image has the tier).  The work order is heaviest tile first, so
+  // the chunks from 16 * heavy on have empty block lists -- known here from
+  // the setup's status words, nothing is read back at frame time.
+  {
+    vxtier::Config tc;
+    tc.block_lists = lists && a.blist_blocks != 0;
+    tc.chunk_table = a.cdesc_addr != 0;
+    tc.cdesc_first = a.cdesc_first;
+    tc.compact = compact;
+    tc.sharded = p->shard_count > 1;
+    tc.path = (p->flags & RT_RENDER_PATH) != 0;
+    r->bg_mode = 1;
+    if (const char* e = std::getenv("RT_BG_TIER")) r->bg_mode = std::min(2u, (uint32_t)std::max(0, std::atoi(e)));
+    r->bg_cost = vxtier::kDefaultCost;
+    if (const char* e = std::getenv("RT_BG_COST")) r->bg_cost = std::atof(e);
+    const char* bs = std::getenv("RT_BG_STALE");
+    r->bg_stale = bs && std::atoi(bs) != 0;
+    const uint32_t chunks = (a.num_tasks + 63u) / 64u;
+    r->bg_first = vxtier::first_bg_chunk(chunks, heavy);
+    r->bg_ok = vxtier::eligible(tc) && r->set_tag && !raster && !tail && !r->deep && !bvh_walk &&
+               !(p->flags & RT_RENDER_FLAT) && r->bg_first != 0 && r->bg_first != chunks;
+    r->img_shape_known[0] = r->img_shape_known[1] = false;
+    rt_tier_arg_t ta{};
+    ta.bg_first_chunk = r->bg_ok ? r->bg_first : chunks;
+    if (r->copy_async ? r->copy_async(r->args, &ta, RT_TIER_ARG_OFFSET, sizeof(ta)) != 0
+                      : vx_copy_to_dev(r->args, &ta, RT_TIER_ARG_OFFSET, sizeof(ta)) != 0)
+      return fail("render argument upload failed");
+  }
   r->setup.device = device ? 1u : 0u;
   r->setup.launches = launches;
   r->setup.heavy_tiles = heavy;
@@ -1320,6 +1380,7 @@ int render_start(rt_renderer_h r, bool sync, uint32_t accum_k) {
     lw[3] |= ((accum_k - 1u) << RT_LW_ACCUM_K_SHIFT) | (r->accum_reset ? RT_LW_ACCUM_RESET : 0u);
   auto start = [&](vx_buffer_h img) {
     if (r->set_words && r->set_words(r->dev, lw, 4) != 0) return false;
+    uint32_t grid = 0;  // the grid asked for (0: the image's)
     if (flip && !r->lane_break) {  // a frame on a launch lane, on the overlapped frames' grid
       if (r->set_lane(r->dev, buf) != 0) return false;
       // (not while the light-space lists are stale: those frames' shadow rays walk the BVH,
@@ -1327,7 +1388,15 @@ int render_start(rt_renderer_h r, bool sync, uint32_t accum_k) {
       // moving_light 0.0184 -> 0.0192 ms)
       const uint32_t g = r->sl_stale ? 0u : lane_grid_of(r);
       if (g != 0 && r->set_grid(r->dev, g) != 0) return false;
+      grid = g;
     }
+    // the background tier: the frame's grid dealt in a geometry and a background tier by its tag
+    for (int ki = 0; ki < 2 && r->bg_ok; ++ki)
+      if (img == r->krnl[0][ki] && !accum_k) {
+        const uint32_t tg = tier_groups_of(r, ki, grid, flip && !r->lane_break);
+        if (tg != 0 && r->set_tag(r->dev, tg) != 0) return false;
+        break;
+      }
     if (vx_start(r->dev, img, r->args) != 0) return false;
     r->lane_break = false;
     r->prev_buf = flip ? r->cur_buf : -1;  // (a frame into the buffer in use keeps no earlier one)

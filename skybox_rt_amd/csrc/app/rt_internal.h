@@ -151,6 +151,17 @@ struct rt_renderer {
   bool lane_grid_known = false;
   vx_hip_set_launch_grid_t set_grid = nullptr;
   vx_hip_image_launch_shape_t launch_shape = nullptr;
+  // the background tier (runtime/bg_tier.h): a frame of an eligible
+  // configuration carries the number of its geometry-tier workgroups as its launch tag
+  // (rt_kernel deals the workgroups behind them the chunks from bg_first on, which it renders
+  // by a lean body); the grid stays the frame's
+  uint32_t bg_mode = 0;      // env RT_BG_TIER: 0 never, 1 frames on a launch lane, 2 every frame
+  bool bg_stale = false;     // env RT_BG_STALE=1: also frames whose light-space lists are stale
+  double bg_cost = 0.0;      // env RT_BG_COST: a geometry chunk's cost in background chunks
+  bool bg_ok = false;        // this configuration may be tiered
+  uint32_t bg_first = 0;     // its first background chunk (16 * heavy tiles)
+  uint32_t img_block[2] = {0, 0}, img_grid[2] = {0, 0};  // rt_kernel / rt_kernel_stats' launch shape
+  bool img_shape_known[2] = {false, false};
   rt_render_params_t params{};
   rt_kernel_arg_t arg{};
   bool configured = false;

@@ -256,6 +256,16 @@ typedef struct {
   uint64_t accum_addr;
   uint64_t pad;
 } rt_accum_arg_t;
+// The background tier's argument area (rt_kernel.hip RT_BG_TIER), behind the two above, which
+// stay where they are: constant from one configure to the next, so the frames in flight may
+// read it.  What changes per launch -- the number of geometry-tier workgroups -- is the
+// launch's tag.
+typedef struct {
+  uint32_t bg_first_chunk;  // the first chunk of the work order behind the tiles geometry reaches
+                            // (16 * heavy tiles): every chunk from here on has an empty block list
+  uint32_t pad[3];
+} rt_tier_arg_t;
+#define RT_TIER_ARG_OFFSET (sizeof(rt_kernel_arg_t) + sizeof(rt_accum_arg_t))
 // padding entries after the last tail list (the first tail pid): the fold
 // loads the entry two ahead and the record one ahead of the one it tests
 #define RT_OLIST_PAD 2u

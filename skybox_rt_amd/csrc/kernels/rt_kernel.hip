@@ -43,6 +43,14 @@
 #ifndef RT_PATHQ
 #define RT_PATHQ 0  // 1: image pt_primary, the path tracer's first kernel (rt_trace.h pathq_append)
 #endif
+// 1 (rt_kernel, rt_kernel_stats): a launch with a tag deals its workgroups in a geometry and a
+// background tier (bg_tier below)
+#ifndef RT_BG_TIER
+#define RT_BG_TIER 0
+#endif
+#if RT_BG_TIER && (RT_FLAT || RT_PATHQ || RT_BVH_WALK || !RT_CHUNK_DESC)
+#error "RT_BG_TIER is for the primary+shadow list image with the chunk descriptor table"
+#endif
 
 namespace {
 
@@ -412,6 +420,99 @@ __device__ __forceinline__ void flat_chunk(const vx_task_t& task, bool valid, co
 // which the driver zeroes before every launch and vx_mpm_query() reads back.
 __device__ __forceinline__ void flush(int slot, uint32_t v) { vx_mpm_add(RT_MPM_USER + slot, v); }
 
+#if RT_BG_TIER
+// The background tier.  A tiered launch (launch tag Tg
+// != 0: the host's choice, runtime/bg_tier.h) deals its chunks in two ranges
+// of the work order: workgroups [0, Tg) take the chunks of the tiles geometry
+// reaches, [0, bg_first_chunk), through kernel_body as ever; the workgroups
+// behind them take the chunks from bg_first_chunk on, whose block lists are
+// all empty (the work order is heaviest tile first and bg_first_chunk = 16 *
+// the tiles of weight > 0; a block with a list entry lies in a tile of weight
+// > 0).  For such a chunk kernel_body finds no winner in any lane and queues
+// no shadow ray: what it leaves is the layers, the shade and the store, which
+// is all bg_tier runs -- the same functions on the same arguments, so pixels
+// and counters are those of kernel_body.  A code path of its own from the
+// wave's first instruction on: the geometry path's scene load, chunk loop and
+// queue never see it.
+//
+// The scene fields resolve_layers / shade_wave / store_out read, and the
+// chunk table; everything else stays 0 and is dead.
+__device__ __forceinline__ Scene load_scene_bg(const rt_kernel_arg_t* ga, const vx_launch_words_t& lw) {
+  const uint64_t p = (uint64_t)ga;
+  const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)p);
+  const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(p >> 32));
+  const __attribute__((address_space(4))) rt_kernel_arg_t* a =
+      (const __attribute__((address_space(4))) rt_kernel_arg_t*)(((uint64_t)hi << 32) | (uint64_t)lo);
+  Scene s;
+  s.argp = (uint64_t)a;
+  s.A = vx_arena::get();
+  s.nodes = s.nodes4 = s.tris = s.ptris = s.geom = s.order = 0;
+  s.vnodes = s.vtris = s.vgeom = s.num_vnodes = 0;
+  s.num_nodes = s.num_nodes4 = s.num_geom = s.flags = 0;
+  s.shard_index = s.shard_count = s.tiles_x = s.bounces = s.seed = s.split_tiles = s.split_log = 0;
+  s.tiles_x_magic = 0;
+  s.sx = s.sy = s.light[0] = s.light[1] = s.light[2] = 0.0f;
+  s.blist = s.bidx = s.blist_blocks = 0;
+  s.sidx = s.slist = s.slist_on = s.slist_n = 0;
+  s.vlayers = (uint32_t)a->vlayers_addr;
+  s.num_layer = a->num_layer_tris;
+  s.prims = (uint32_t)a->prims_addr;
+  s.dcs = (uint32_t)a->dcs_addr;
+  s.cbuf = (uint32_t)a->cbuf_addr;
+  s.width = a->width;
+  s.height = a->height;
+  s.clear_color = a->clear_color;
+  s.num_tasks = a->num_tasks;
+  s.cdesc = (uint32_t)a->cdesc_addr;
+  s.cdesc_first = a->cdesc_first;
+  s.lw3 = lw.w[3];
+  return s;
+}
+
+__device__ __forceinline__ uint32_t bg_first_chunk(const rt_kernel_arg_t* ga) {
+  const uint64_t p = (uint64_t)ga + RT_TIER_ARG_OFFSET;
+  const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)p);
+  const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(p >> 32));
+  return ((const __attribute__((address_space(4))) rt_tier_arg_t*)(((uint64_t)hi << 32) | (uint64_t)lo))
+      ->bg_first_chunk;
+}
+
+// A background-tier wave: wave (blockIdx.x - tg) * kWaves + its index in the
+// workgroup of the (gridDim.x - tg) * kWaves that share the chunks
+// [bg_first_chunk, chunks).  No LDS, no queue, no drain.
+__device__ __forceinline__ void bg_tier(const rt_kernel_arg_t* arg, uint32_t tg, const vx_launch_words_t& lw) {
+  const Scene S = load_scene_bg(arg, lw);
+  Counters cnt;
+  const uint32_t nchunks = (S.num_tasks + VX_CHUNK - 1) / VX_CHUNK;
+  const uint32_t nw = (gridDim.x - tg) * kWaves;  // (blockIdx.x >= tg: at least kWaves)
+  uint32_t ran = 0;
+  // (the wave's index as a scalar: the chunk loop is a scalar loop, no exec mask kept across it)
+  const uint32_t wv = (uint32_t)__builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  for (uint32_t c = bg_first_chunk(arg) + (blockIdx.x - tg) * kWaves + wv; c < nchunks; c += nw) {
+    const uint32_t ln = threadIdx.x & 63u;
+    if (c * VX_CHUNK + ln < S.num_tasks) {
+      const uint4 d = S.A.sld_u4(S.cdesc + 16u * (c - S.cdesc_first));
+      const uint32_t x = (d.x & 0xffffu) + (ln & 7u);
+      const uint32_t y = (d.x >> 16) + (ln >> 3);
+      const uint32_t out = d.y + (ln >> 3) * (d.w >> 16) + (ln & 7u);
+      const bool in = x < S.width && y < S.height;
+      cnt.primary += in;
+      const int32_t spid = resolve_layers(S, x, y, in, -1, cnt);
+      const uint32_t color = shade_wave(S, spid, x, y, S.clear_color, cnt);
+      if (in) store_out(S, out, color);
+      ++ran;
+    }
+  }
+  vx_mpm_add(VX_MPM_TASKS, ran);
+  flush(RT_STAT_PRIMARY, cnt.primary);
+#ifdef RT_INSTRUMENT
+  flush(RT_STAT_LAYER_TESTS, cnt.layer_tests);
+  flush(RT_STAT_SHADED, cnt.shaded);
+  flush(RT_STAT_TEXEL_BYTES, cnt.texel_bytes);
+#endif
+}
+#endif
+
 }  // namespace
 
 // primary + shadow images: registers for 7 waves per SIMD (<= 72 VGPRs: 67,
@@ -444,6 +545,14 @@ VX_MAIN_OCC(rt_kernel_arg_t, arg, RT_BLOCK_THREADS, RT_WAVES_PER_EU) {
 #else
 VX_MAIN(rt_kernel_arg_t, arg, RT_BLOCK_THREADS) {
 #endif
+#if RT_BG_TIER
+  // a tiered launch (tag = its geometry-tier workgroups): the workgroups behind them run the
+  // background tier and nothing of what follows
+  if (vx_launch_tag != 0 && blockIdx.x >= vx_launch_tag) {
+    bg_tier(arg, vx_launch_tag, vx_launch_words);
+    return 0;
+  }
+#endif
   __shared__ WaveLds s_wave[kWaves];
   WaveLds& w = s_wave[threadIdx.x >> 6];
 #ifdef RT_STAMPS
@@ -470,10 +579,21 @@ VX_MAIN(rt_kernel_arg_t, arg, RT_BLOCK_THREADS) {
 #else
   if ((threadIdx.x & 63u) == 0) w.q_count = 0;
   __builtin_amdgcn_wave_barrier();
+#if RT_BG_TIER
+  // the geometry tier of a tiered launch: its tag's workgroups share the chunks below
+  // bg_first_chunk; tag 0: the grid's waves share every chunk, vx_spawn_tasks_ex's deal
+  const uint32_t tier_wgs = vx_launch_tag != 0 ? vx_launch_tag : gridDim.x;
+  const uint32_t tier_end = vx_launch_tag != 0 ? bg_first_chunk(arg) : 0xffffffffu;
+  const int rc = vx_spawn_chunks_ex(
+      S.num_tasks, 0u, tier_end, blockIdx.x * kWaves + (threadIdx.x >> 6), tier_wgs * kWaves,
+      [&](const vx_task_t& task, const Scene* s) { kernel_body(task, *s, w, cnt); },
+      [&](bool final, const Scene* s) { shadow_drain(final, *s, w, cnt); }, &S);
+#else
   const int rc = vx_spawn_tasks_ex(
       S.num_tasks,
       [&](const vx_task_t& task, const Scene* s) { kernel_body(task, *s, w, cnt); },
       [&](bool final, const Scene* s) { shadow_drain(final, *s, w, cnt); }, &S);
+#endif
 #endif
 #ifdef RT_STAMPS  // diagnostic image: per-wave phase timestamps
   if (threadIdx.x == 0) {

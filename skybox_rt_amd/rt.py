@@ -69,7 +69,8 @@ class SetupStats(C.Structure):
                 ("blist_blocks", C.c_uint32), ("setup_ms", C.c_double), ("configure_ms", C.c_double),
                 ("blist_entries", C.c_uint64), ("blist_max", C.c_uint32), ("slist_on", C.c_uint32),
                 ("slist_entries", C.c_uint64), ("path_queue", C.c_uint32), ("slist_built", C.c_uint32),
-                ("slist_stale", C.c_uint32), ("lane_grid", C.c_uint32)]
+                ("slist_stale", C.c_uint32), ("lane_grid", C.c_uint32),
+                ("bg_first_chunk", C.c_uint32), ("tier_groups", C.c_uint32)]
 
     def as_dict(self):
         return {n: getattr(self, n) for n, _ in self._fields_ if n != "pad"}
