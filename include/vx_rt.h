@@ -383,6 +383,52 @@ int rt_renderer_set_light(rt_renderer_h r, const float light[3]);
  * NO REFERENCE. */
 int rt_renderer_set_list_policy(rt_renderer_h r, uint32_t defer_frames);
 
+/* Several point lights, traced in one launch.  NO REFERENCE (the reference
+ * has one light; none of the entry points below has a counterpart there).
+ *
+ * A frame lit by lights L_0 .. L_{n-1} (1 <= n <= RT_MAX_LIGHTS) is, per
+ * pixel and colour channel, the rounded mean of the n RT_RENDER_SHADOWS
+ * frames of the single lights: mean = (2 * sum + n) / (2 * n) in integer
+ * division (rt_accum_resolve on {sums, n}); the alpha byte is the primary
+ * colour's.  A single-light frame stores a shadow ray's colour c or c >> 1
+ * per channel, so with o = the lights that do not see the ray, sum = (n - o)
+ * * c + o * (c >> 1) (rt_lights_resolve); a pixel without a shadow ray is c.
+ * Primary visibility, layers, shading and texel reads run once per frame; in
+ * the drain every packet of queued shadow rays is tested against each light
+ * in turn, on that light's own light-space lists or, for a light whose lists
+ * do not fit, by the BVH packet walk (images rt_lights / rt_lights_stats).
+ *
+ * rt_renderer_set_lights: valid on a configured plain RT_RENDER_SHADOWS
+ * frame on the binary16 BVH4 (RT_RENDER_COUNTERS, INSTRUMENTED, COMPACT,
+ * shards and HOST_SETUP as usual).  It builds one set of lists per light at
+ * once -- no deferral; with env RT_SHADOW_LISTS=0 or under RT_RENDER_HOST_SETUP
+ * none, every light walks the BVH -- reads each set's status and uploads the
+ * light table: it WAITS FOR THE DEVICE, like a configure.  -2 (rt_last_error
+ * says why) for n outside 1..16, a configuration without RT_RENDER_SHADOWS or
+ * with RT_RENDER_PATH / FLAT / RASTER / BVH_WALK, a scene with a non-empty
+ * ordered tail (RT_SCENE_OM_LAYERS), a tree the generic (deep) images run, a
+ * kernel directory without rt_lights.vxbin.  With n >= 2 the frames after it
+ * (rt_render, rt_render_start) are ordinary launches of the new image on its
+ * own grid into the framebuffer in use -- no launch lane, no overlap.  n = 1
+ * is rt_renderer_set_light under list policy 0.  rt_renderer_set_light and
+ * rt_renderer_configure return to one light. */
+#define RT_MAX_LIGHTS 16u
+int rt_renderer_set_lights(rt_renderer_h r, const float (*lights)[3], uint32_t n);
+typedef struct {
+  float light[3];
+  uint32_t slist_on;       /* 1: the light's shadow rays scan its light-space lists; 0: walk the BVH */
+  uint64_t slist_entries;  /* entries of its lists (also when they did not fit) */
+} rt_light_info_t;
+/* the lights in use (one entry after set_light / configure), at most max; *n = their number */
+int rt_renderer_lights_info(rt_renderer_h r, rt_light_info_t* out, uint32_t max, uint32_t* n);
+/* light `light`'s list arrays, which = RT_REC_SIDX or RT_REC_SLIST, as
+ * rt_renderer_export_records gives the single light's (out NULL = size query) */
+int rt_renderer_export_light_lists(rt_renderer_h r, uint32_t light, uint32_t which, void* out, uint64_t bytes,
+                                   uint64_t* size);
+/* the host restatement of the device resolve: the pixel of a shadow ray of
+ * primary colour argb that `occluded` of its k lights do not see */
+uint32_t rt_lights_resolve(uint32_t argb, uint32_t occluded, uint32_t k);
+
 /* Read back one per-resolution record array of the current configuration
  * (layouts: kernels/rt_common.h; NO REFERENCE).  out NULL = size query
  * (*size = bytes). */

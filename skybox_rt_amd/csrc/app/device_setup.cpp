@@ -234,40 +234,41 @@ uint32_t slist_res() {
   return N;
 }
 
-// the shadow-list fields of the setup argument block for the light in r->arg
-// (buffers grown to the light-space cells and the entry capacity r->su.scap)
-int slist_args(rt_renderer* r, rt_setup_arg_t* g) {
+// the shadow-list fields of the setup argument block for a list set and its light (the set's
+// buffers grown to the light-space cells and its entry capacity; the chain's scratch, which
+// every set shares, to the largest capacity asked for so far)
+int slist_args(rt_renderer* r, rt_setup_arg_t* g, const ListSet& ls, const float light[3]) {
   rt_kernel_arg_t& a = r->arg;
   const uint32_t N = slist_res(), cells = 6u * N * N;
   const uint32_t ncpart = (cells + RTS_BLOCKS_PER_PART - 1) / RTS_BLOCKS_PER_PART;
   const uint64_t items = 6ull * r->sc->geometry.size();
-  if (r->su.scap == 0) {
+  if (*ls.cap == 0) {
     // initial entry capacity (env RT_SETUP_SCAP: tests force the overflow refill)
-    r->su.scap = 1u << 19;
-    if (const char* e = std::getenv("RT_SETUP_SCAP")) r->su.scap = std::max(1u, (uint32_t)std::atoi(e));
+    *ls.cap = 1u << 19;
+    if (const char* e = std::getenv("RT_SETUP_SCAP")) *ls.cap = std::max(1u, (uint32_t)std::atoi(e));
   }
   if (ensure(r, (uint64_t)cells * 4, &r->su.scnt) || ensure(r, (uint64_t)ncpart * 4, &r->su.spart) ||
-      ensure(r, (uint64_t)cells * 8, &r->sidx, &a.sidx_addr) ||
+      ensure(r, (uint64_t)cells * 8, ls.sidx, ls.sidx_addr) ||
       ensure(r, items * RTS_SPROJ_WORDS * 4, &r->su.sproj) || ensure(r, (items + 1) * 4, &r->su.soff) ||
       ensure(r, r->sc->geometry.size() * 4, &r->su.skey) ||
-      ensure(r, 3ull * r->su.scap * 4, &r->su.stmp) ||
-      ensure(r, ((uint64_t)r->su.scap + 1) * sizeof(rt_tri_t), &r->slist, &a.slist_addr))
+      ensure(r, 3ull * *ls.cap * 4, &r->su.stmp) ||
+      ensure(r, ((uint64_t)*ls.cap + 1) * sizeof(rt_tri_t), ls.slist, ls.slist_addr))
     return -1;
   a.slist_n = N;
   g->geom_addr = a.geom_addr;
   g->slist_n = N;
-  for (int i = 0; i < 3; ++i) g->light[i] = a.light[i];
+  for (int i = 0; i < 3; ++i) g->light[i] = light[i];
   g->scnt_addr = r->su.scnt.addr;
   g->spart_addr = r->su.spart.addr;
-  g->sidx_addr = a.sidx_addr;
+  g->sidx_addr = *ls.sidx_addr;
   g->sproj_addr = r->su.sproj.addr;
   g->soff_addr = r->su.soff.addr;
   g->skey_addr = r->su.skey.addr;
   g->stmp_addr = r->su.stmp.addr;
-  g->slist_addr = a.slist_addr;
+  g->slist_addr = *ls.slist_addr;
   g->ncells = cells;
   g->ncpart = ncpart;
-  g->scap = r->su.scap;
+  g->scap = *ls.cap;
   g->fold = fold_flags(r);  // a refill reads the counts the way the chain left them
   return 0;
 }
@@ -280,16 +281,16 @@ void list_limits(rt_setup_arg_t* g) {
   g->max_entries = (uint32_t)std::min<uint64_t>(cap, 0xffffffffu);
 }
 
-// after a chain that built the shadow lists: their verdict from the status
-// words; an overflow of the entry capacity (only when the lists would be
+// after a chain that built a set's shadow lists (for ls.light): their verdict from the
+// status words; an overflow of the entry capacity (only when the lists would be
 // used) grows it to the exact size and refills: cursors zeroed, SFILL, SSORT
-int slist_finish(rt_renderer* r, rt_setup_arg_t& g, uint32_t st[RTS_STATUS_WORDS], uint32_t* launches) {
-  r->sl_entries = st[5];
-  r->setup.slist_entries = st[5];
+int slist_finish(rt_renderer* r, rt_setup_arg_t& g, uint32_t st[RTS_STATUS_WORDS], uint32_t* launches,
+                 const ListSet& ls) {
+  *ls.entries = st[5];
   const bool fit = block_lists_fit(st[4], st[5]);
   if (fit && st[7] != 0) {
-    r->su.scap = st[5];
-    if (slist_args(r, &g) != 0) return -1;
+    *ls.cap = st[5];
+    if (slist_args(r, &g, ls, ls.light) != 0) return -1;
     g.nfills = 0;
     add_fill(&g, r->su.scnt.addr, g.ncells, 0u);
     add_fill(&g, r->su.status.addr + 28, 1, 0u);  // the overflow word
@@ -300,10 +301,38 @@ int slist_finish(rt_renderer* r, rt_setup_arg_t& g, uint32_t st[RTS_STATUS_WORDS
     if (run_seq(r, g, q, launches) != 0 || read_status(r, st) != 0) return -1;
     if (st[7] != 0) return set_error("shadow-list refill overflowed its exact capacity");
   }
-  r->sl_pending = false;
-  r->sl_built = fit;
-  r->sl_rejected = !fit;
+  *ls.built = fit;
+  *ls.rejected = !fit;
   return 0;
+}
+// set 0, the renderer's own lists: the setup statistics follow them
+int slist_finish0(rt_renderer* r, rt_setup_arg_t& g, uint32_t st[RTS_STATUS_WORDS], uint32_t* launches) {
+  r->setup.slist_entries = st[5];
+  if (slist_finish(r, g, st, launches, r->set0()) != 0) return -1;
+  r->sl_pending = false;
+  return 0;
+}
+
+// the chain that builds one set's lists for `light`, queued on the driver's stream; rargs: the
+// render arguments whose slist_on the chain's last launch writes (0: none)
+int queue_set(rt_renderer* r, rt_setup_arg_t& g, const ListSet& ls, const float light[3], uint64_t rargs,
+              uint32_t* launches) {
+  base_arg(r, &g);
+  list_limits(&g);
+  g.status_addr = r->su.status.addr;
+  if (slist_args(r, &g, ls, light) != 0) return -1;
+  g.rargs_addr = rargs;
+  add_fill(&g, g.scnt_addr, g.ncells, 0u);
+  add_fill(&g, g.status_addr + 16, 4, 0u);  // status words 4..7: the shadow lists
+  g.fold = fold_flags(r);
+  Seq q;
+  q.add(RTS_FILL | RTS_SPROJ, (g.fold & RTS_FOLD_SOFF) ? 0u : RTS_SOSCAN);
+  q.add(RTS_SCOUNT);
+  q.add(RTS_SSUM, (g.fold & RTS_FOLD_LISTS) ? 0u : RTS_SSCAN);
+  q.add(RTS_SOFF);
+  q.add(RTS_SFILL);
+  q.add(RTS_SSORT);
+  return run_seq(r, g, q, launches);
 }
 
 }  // namespace
@@ -414,7 +443,7 @@ int device_setup(rt_renderer* r, bool raster, bool order_on, bool lists, bool sl
                                   std::memcmp(r->sl_light, a.light, sizeof(a.light)) == 0);
   r->setup.slist_built = sl_now ? 1u : 0u;
   if (sl_now) {
-    if (slist_args(r, &g) != 0) return -1;
+    if (slist_args(r, &g, r->set0(), a.light) != 0) return -1;
     add_fill(&g, g.scnt_addr, g.ncells, 0u);
   }
   const uint32_t ord = order_on ? 1u : 0u, bl = lists ? 1u : 0u, sl = sl_now ? 1u : 0u;
@@ -468,7 +497,7 @@ int device_setup(rt_renderer* r, bool raster, bool order_on, bool lists, bool sl
   if (sl_now) {
     std::memcpy(r->sl_light, a.light, sizeof(a.light));
     r->sl_n = N;
-    if (slist_finish(r, g, st, launches) != 0) return -1;
+    if (slist_finish0(r, g, st, launches) != 0) return -1;
   } else if (slists) {
     r->setup.slist_entries = r->sl_entries;
     a.slist_n = N;
@@ -563,24 +592,9 @@ int queue_lists(rt_renderer* r, uint32_t* launches) {
   // so no host wait anywhere; the status words are read when asked for
   // (rt_renderer_setup_stats) or by the next configure
   rt_setup_arg_t g;
-  base_arg(r, &g);
-  list_limits(&g);
-  g.status_addr = r->su.status.addr;
-  if (slist_args(r, &g) != 0) return -1;
   uint64_t rargs = 0;
   if (vx_mem_address(r->args, &rargs) != 0) return set_error("vx_mem_address failed");
-  g.rargs_addr = rargs;
-  add_fill(&g, g.scnt_addr, g.ncells, 0u);
-  add_fill(&g, g.status_addr + 16, 4, 0u);  // status words 4..7: the shadow lists
-  g.fold = fold_flags(r);
-  Seq q;
-  q.add(RTS_FILL | RTS_SPROJ, (g.fold & RTS_FOLD_SOFF) ? 0u : RTS_SOSCAN);
-  q.add(RTS_SCOUNT);
-  q.add(RTS_SSUM, (g.fold & RTS_FOLD_LISTS) ? 0u : RTS_SSCAN);
-  q.add(RTS_SOFF);
-  q.add(RTS_SFILL);
-  q.add(RTS_SSORT);
-  if (run_seq(r, g, q, launches) != 0) return -1;
+  if (queue_set(r, g, r->set0(), a.light, rargs, launches) != 0) return -1;
   std::memcpy(r->sl_light, a.light, sizeof(a.light));
   r->sl_n = a.slist_n;
   r->sl_pending = true;
@@ -600,7 +614,7 @@ int settle_lists(rt_renderer* r) {
   g.rargs_addr = rargs;
   uint32_t launches = 0;
   const uint64_t sidx0 = r->arg.sidx_addr, slist0 = r->arg.slist_addr;
-  if (slist_finish(r, g, st, &launches) != 0) return -1;
+  if (slist_finish0(r, g, st, &launches) != 0) return -1;
   r->arg.slist_on = r->sl_built ? 1u : 0u;
   if (r->arg.sidx_addr != sidx0 || r->arg.slist_addr != slist0) {
     // a refill moved the lists: the render arguments' addresses follow (the
@@ -609,6 +623,25 @@ int settle_lists(rt_renderer* r) {
     const size_t n = offsetof(rt_kernel_arg_t, slist_addr) + sizeof(uint64_t) - o;
     if (vx_copy_to_dev(r->args, reinterpret_cast<const uint8_t*>(&r->arg) + o, o, n) != 0)
       return set_error("vx_copy_to_dev failed");
+  }
+  return 0;
+}
+
+int build_light_sets(rt_renderer* r, const float (*lights)[3], uint32_t n, bool lists, uint32_t* launches) {
+  if (r->lsets.size() < n) r->lsets.resize(n);
+  // the status words are the renderer's one set: lists of its own still unsettled go first
+  if (r->sl_pending && settle_lists(r) != 0) return -1;
+  for (uint32_t i = 0; i < n; ++i) {
+    LightSet& l = r->lsets[i];
+    std::memcpy(l.light, lights[i], sizeof(l.light));
+    l.built = l.rejected = false;
+    l.entries = 0;
+    if (!lists) continue;
+    rt_setup_arg_t g;
+    uint32_t st[RTS_STATUS_WORDS];
+    if (queue_set(r, g, l.set(), l.light, 0, launches) != 0 || read_status(r, st) != 0 ||
+        slist_finish(r, g, st, launches, l.set()) != 0)
+      return -1;
   }
   return 0;
 }

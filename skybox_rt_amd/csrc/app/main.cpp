@@ -17,7 +17,8 @@
 // mixed depth functions: DESIGN.md "Scope") and any -k other than the
 // RASTER_TILE_LOGSIZE 5 the RT path bins at render through the draw3d raster
 // pipeline instead, which is what draw3d itself runs.  Extensions: -S shadow
-// rays, -L x,y,w light, -P N path tracing with N bounces, -F flat triangle
+// rays, -L x,y,w light, -M x,y,w one more light (repeatable: with -S the
+// frame is lit by the light of -L and every -M, rt_renderer_set_lights), -P N path tracing with N bounces, -F flat triangle
 // list, -R raster pipeline, -n N repeat launches, -B lbvh|sah device BVH
 // build, -H host-loop setup, -O load the scene with RT_SCENE_OM_LAYERS (a
 // scene the RT path cannot trace as a whole renders on the RT path all the
@@ -42,6 +43,7 @@
 #include <fstream>
 #include <string>
 #include <vector>
+#include <array>
 
 #include <sys/stat.h>
 #include <unistd.h>
@@ -71,6 +73,7 @@ const char* build = nullptr;          // -B lbvh|sah: build the BVH on the devic
 bool host_setup = false;              // -H: per-resolution records by the host loops
 bool om_layers = false;               // -O: RT_SCENE_OM_LAYERS
 uint32_t accum_samples = 0;           // -A: with -P, accumulate this many samples per pixel
+std::vector<std::array<float, 3>> more_lights;  // -M: lights beside the one of -L
 
 #ifdef RT_APP_RASTER
 const char* kOpts = "t:i:o:r:w:h:k:n:z?";
@@ -80,12 +83,12 @@ void usage() {
               "[-k tilelogsize] [-n repeat]\n");
 }
 #else
-const char* kOpts = "t:s:e:i:o:r:w:h:k:n:L:P:G:I:B:A:uxyzSRFHO?";
+const char* kOpts = "t:s:e:i:o:r:w:h:k:n:L:M:P:G:I:B:A:uxyzSRFHO?";
 void usage() {
   std::printf("Vortex 3D Rendering Test (MI355X).\n"
               "Usage: [-t trace] [-s startdraw] [-e enddraw] [-o output] [-r reference] [-w width] "
               "[-h height] [-x s/w rast] [-y s/w om] [-u s/w tex] [-k tilelogsize]\n"
-              "       [-S shadows] [-L x,y,w] [-n repeat] [-R raster | -P bounces | -F flat] "
+              "       [-S shadows] [-L x,y,w] [-M x,y,w one more light, repeatable] [-n repeat] [-R raster | -P bounces | -F flat] "
               "[-G rank,ranks [-I idfile]] [-B lbvh|sah device BVH build] [-H host setup]\n"
               "       [-O trace the head, fold blended / stencil / masked drawcalls (RT_SCENE_OM_LAYERS)]\n"
               "       [-A samples: with -P, accumulate that many samples per pixel on the device and "
@@ -125,6 +128,12 @@ int main(int argc, char** argv) {
     case 'F': flat = true; break;
     case 'P': bounces = std::atoi(optarg); break;
     case 'L': std::sscanf(optarg, "%f,%f,%f", &light[0], &light[1], &light[2]); break;
+    case 'M': {
+      std::array<float, 3> m = {0.0f, 0.0f, 0.0f};
+      std::sscanf(optarg, "%f,%f,%f", &m[0], &m[1], &m[2]);
+      more_lights.push_back(m);
+      break;
+    }
     case 'G': std::sscanf(optarg, "%d,%d", &rank, &ranks); break;
     case 'I': id_file = optarg; break;
     case 'B': build = optarg; break;
@@ -151,6 +160,10 @@ int main(int argc, char** argv) {
     }
     std::printf("Tile log size %d: rendering through the draw3d raster pipeline\n", tile_log);
     raster = true;
+  }
+  if (!more_lights.empty() && (!shadows || more_lights.size() + 1 > RT_MAX_LIGHTS)) {
+    std::printf("Error: -M x,y,w needs -S (shadow rays), at most %u lights in all\n", RT_MAX_LIGHTS);
+    return 1;
   }
   if (accum_samples && (bounces < 0 || rank >= 0)) {
     std::printf("Error: -A samples needs -P bounces (path tracing), one rank\n");
@@ -251,6 +264,14 @@ int main(int argc, char** argv) {
   RT_CHECK(rt_renderer_setup_stats(r, &ss));
   std::printf("Setup (%s): %.3f ms, configure %.3f ms\n", ss.device ? "device" : "host", ss.setup_ms,
               ss.configure_ms);
+  if (!more_lights.empty()) {
+    // the light of -L first, then every -M in order
+    std::vector<float> ls(light, light + 3);
+    for (const auto& m : more_lights) ls.insert(ls.end(), m.begin(), m.end());
+    const uint32_t nl = (uint32_t)more_lights.size() + 1u;
+    RT_CHECK(rt_renderer_set_lights(r, reinterpret_cast<const float(*)[3]>(ls.data()), nl));
+    std::printf("Lights: %u, traced in one launch\n", nl);
+  }
   double total = 0.0;
   rt_stats_t st;
   std::vector<uint32_t> gathered;

@@ -557,6 +557,7 @@ int rt_renderer_set_light(rt_renderer_h r, const float light[3]) {
   if (!(r->params.flags & (RT_RENDER_SHADOWS | RT_RENDER_PATH)) || (r->params.flags & RT_RENDER_RASTER))
     return fail("rt_renderer_set_light: the configuration traces no shadow rays");
   uint32_t launches = 0;
+  r->nlights = 0;  // back to one light (rt_renderer_set_lights)
   if (rtapp::set_light(r, light, &launches) != 0) return -1;
   r->setup.slist_built = r->sl_mode ? 1u : 0u;
   // a moved light changes what the accumulated samples estimate: the next
@@ -566,6 +567,123 @@ int rt_renderer_set_light(rt_renderer_h r, const float light[3]) {
     r->accum_n = 0;
   }
   return 0;
+}
+
+// ---- several lights (vx_rt.h; NO REFERENCE) --------------------------------
+
+int rt_renderer_set_lights(rt_renderer_h r, const float (*lights)[3], uint32_t n) {
+  if (!r) return fail("null argument");
+  if (!r->configured) return fail("renderer not configured");
+  if (n < 1 || n > RT_MAX_LIGHTS) return fail("rt_renderer_set_lights: 1 to 16 lights", -2);
+  if (!lights) return fail("null argument");
+  const uint32_t f = r->params.flags;
+  if (!(f & RT_RENDER_SHADOWS) || (f & (RT_RENDER_PATH | RT_RENDER_FLAT | RT_RENDER_RASTER | RT_RENDER_BVH_WALK)))
+    return fail("rt_renderer_set_lights: a plain RT_RENDER_SHADOWS frame only (no RT_RENDER_PATH / FLAT / RASTER / "
+                "BVH_WALK)", -2);
+  if (!r->sc->tail_prims.empty())
+    return fail("rt_renderer_set_lights: a scene with an ordered tail renders with one light (rt_om has no "
+                "several-light image)", -2);
+  // (a scene without geometry queues no shadow ray and walks no tree: any image serves it)
+  if (r->arg.num_geom > 0 && (r->deep || !(r->arg.flags & RT_FLAG_BVH4H)))
+    return fail("rt_renderer_set_lights: rt_lights walks the binary16 BVH4 only; this tree runs the generic "
+                "(deep) images", -2);
+  if (!r->krnl_lights[0]) {
+    // next to the rt_kernel.vxbin in use: the kernel directory's when it holds one
+    std::string dir = r->kdir;
+    if (FILE* fk = std::fopen((dir + "/rt_kernel.vxbin").c_str(), "rb")) std::fclose(fk);
+    else dir = lib_dir();
+    const char* names[2] = {"rt_lights.vxbin", "rt_lights_stats.vxbin"};
+    for (int i = 0; i < 2; ++i)
+      if (FILE* fa = std::fopen((dir + "/" + names[i]).c_str(), "rb")) std::fclose(fa);
+      else return fail("rt_renderer_set_lights: no " + std::string(names[i]) + " next to " + dir + "/rt_kernel.vxbin", -2);
+    for (int i = 0; i < 2; ++i)
+      if (vx_upload_kernel_file(r->dev, (dir + "/" + names[i]).c_str(), &r->krnl_lights[i]) != 0) {
+        for (int j = 0; j <= i; ++j) {
+          if (r->krnl_lights[j]) vx_mem_free(r->krnl_lights[j]);
+          r->krnl_lights[j] = nullptr;
+        }
+        return fail("cannot upload kernel " + dir + "/" + names[i]);
+      }
+  }
+  uint32_t launches = 0;
+  if (n == 1) {
+    // one light: rt_renderer_set_light with its lists queued at once
+    const uint32_t defer = r->sl_defer;
+    r->sl_defer = 0;
+    const int e = rt_renderer_set_light(r, lights[0]);
+    r->sl_defer = defer;
+    if (e != 0) return e;
+    return rtapp::settle_lists(r);
+  }
+  // a list set per light, each chain behind the frames in flight; then the table, in stream
+  // order ahead of every frame started after it
+  if (rtapp::build_light_sets(r, lights, n, r->sl_mode, &launches) != 0) return -1;
+  rt_lights_arg_t la{};
+  la.count = n;
+  la.slist_n = r->arg.slist_n;
+  for (uint32_t i = 0; i < n; ++i) {
+    const LightSet& l = r->lsets[i];
+    std::memcpy(la.l[i].light, l.light, sizeof(l.light));
+    la.l[i].slist_on = l.built ? 1u : 0u;
+    la.l[i].sidx_addr = l.sidx_addr;
+    la.l[i].slist_addr = l.slist_addr;
+    if (l.built && ((l.sidx_addr | l.slist_addr) >> 32) != 0) return fail("light-space lists above 4 GiB");
+  }
+  if (r->copy_async ? r->copy_async(r->args, &la, RT_LIGHTS_ARG_OFFSET, sizeof(la)) != 0
+                    : vx_copy_to_dev(r->args, &la, RT_LIGHTS_ARG_OFFSET, sizeof(la)) != 0)
+    return fail("light table upload failed");
+  if (vx_ready_wait(r->dev, VX_MAX_TIMEOUT) != 0) return fail("vx_ready_wait failed");
+  r->nlights = n;
+  r->lane_break = true;
+  return 0;
+}
+
+int rt_renderer_lights_info(rt_renderer_h r, rt_light_info_t* out, uint32_t max, uint32_t* n) {
+  if (!r || !n) return fail("null argument");
+  if (!r->configured) return fail("renderer not configured");
+  if (r->nlights == 0) {
+    if (rtapp::settle_lists(r) != 0) return -1;
+    *n = 1;
+    if (out && max >= 1) {
+      std::memcpy(out[0].light, r->arg.light, sizeof(out[0].light));
+      out[0].slist_on = r->arg.slist_on;
+      out[0].slist_entries = r->sl_mode ? r->sl_entries : 0;
+    }
+    return 0;
+  }
+  *n = r->nlights;
+  for (uint32_t i = 0; out && i < r->nlights && i < max; ++i) {
+    const LightSet& l = r->lsets[i];
+    std::memcpy(out[i].light, l.light, sizeof(out[i].light));
+    out[i].slist_on = l.built ? 1u : 0u;
+    out[i].slist_entries = l.entries;
+  }
+  return 0;
+}
+
+int rt_renderer_export_light_lists(rt_renderer_h r, uint32_t light, uint32_t which, void* out, uint64_t bytes,
+                                   uint64_t* size) {
+  if (!r || !r->configured) return fail("renderer not configured");
+  if (which != RT_REC_SIDX && which != RT_REC_SLIST) return fail("RT_REC_SIDX or RT_REC_SLIST");
+  if (r->nlights == 0) {
+    if (light != 0) return fail("no such light");
+    return rt_renderer_export_records(r, which, out, bytes, size);
+  }
+  if (light >= r->nlights) return fail("no such light");
+  const LightSet& l = r->lsets[light];
+  if (!l.built) return fail("record array not present in this configuration");
+  const uint32_t N = r->arg.slist_n;
+  const uint64_t nb = which == RT_REC_SIDX ? 6ull * N * N * 8 : (l.entries + 1) * sizeof(rt_tri_t);
+  if (size) *size = nb;
+  if (!out) return 0;
+  if (bytes < nb) return fail("buffer too small");
+  return vx_copy_from_dev(out, which == RT_REC_SIDX ? l.sidx : l.slist, 0, nb) == 0
+             ? 0 : fail("vx_copy_from_dev failed");
+}
+
+uint32_t rt_lights_resolve(uint32_t argb, uint32_t occluded, uint32_t k) {
+  if (k < 1 || k > RT_MAX_LIGHTS || occluded > k) return argb;
+  return rt_lights_mix(argb, occluded, k);
 }
 
 int rt_renderer_export_records(rt_renderer_h r, uint32_t which, void* out, uint64_t bytes,
@@ -1063,6 +1181,7 @@ int rt_renderer_configure(rt_renderer_h r, const rt_render_params_t* p) {
   r->accum_on = r->accum_reset = false;
   r->accum_bytes = 0;
   r->accum_n = 0;
+  r->nlights = 0;  // a configure returns to one light (rt_renderer_set_lights)
   rt_kernel_arg_t& a = r->arg;
   a.width = p->width;
   a.height = p->height;
@@ -1284,8 +1403,9 @@ int rt_renderer_configure(rt_renderer_h r, const rt_render_params_t* p) {
   // the setup just queued -- no wait for the device
   // (behind the block, the accumulating path tracer's area: rt_renderer_accum_begin writes it)
   // (and behind that the background tier's: rt_tier_arg_t, constant until the next configure)
+  // (and the light table of rt_renderer_set_lights)
   if (!r->args &&
-      upload(r->dev, nullptr, RT_TIER_ARG_OFFSET + sizeof(rt_tier_arg_t), &r->args, &args_addr))
+      upload(r->dev, nullptr, RT_LIGHTS_ARG_OFFSET + sizeof(rt_lights_arg_t), &r->args, &args_addr))
     return -1;
   if (r->copy_async ? r->copy_async(r->args, &a, 0, sizeof(a)) != 0
                     : vx_copy_to_dev(r->args, &a, 0, sizeof(a)) != 0)
@@ -1355,7 +1475,8 @@ int render_start(rt_renderer_h r, bool sync, uint32_t accum_k) {
   if (!r || !r->configured) return fail("renderer not configured");
   // the moving light: the lists of a light that stayed for sl_defer frames
   // are queued before this frame (the frames before walked the BVH)
-  if (r->sl_stale && ++r->sl_static > r->sl_defer) {
+  // (not under several lights: their frames read their own sets, built by set_lights)
+  if (r->nlights < 2 && r->sl_stale && ++r->sl_static > r->sl_defer) {
     uint32_t launches = 0;
     if (rtapp::queue_lists(r, &launches) != 0) return -1;
   }
@@ -1365,15 +1486,18 @@ int render_start(rt_renderer_h r, bool sync, uint32_t accum_k) {
   // every launch of the frame carries its light (and, while the lists wait
   // for a light that stays, the switch to the BVH walk) in its launch words:
   // rt_renderer_set_light queues no copy
+  // (a frame of several lights reads them from its table: neither launch-word bit)
+  const bool multi = r->nlights >= 2 && !accum_k;
   uint32_t lw[4] = {0, 0, 0, 0};
-  if (r->set_words) {
+  if (r->set_words && !multi) {
     std::memcpy(lw, r->arg.light, sizeof(r->arg.light));
     lw[3] = RT_LW_LIGHT | (r->sl_stale ? RT_LW_NO_SLIST : 0u);
   }
   // frame overlap: this frame's buffer and lane are the other ones than the
   // last frame's; with one buffer the frame is an ordinary launch into the
   // buffer in use (the second one after rt_framebuffer_device handed it out)
-  const bool flip = r->lanes && !sync;
+  // (a frame of several lights: an ordinary launch too, on the image's grid)
+  const bool flip = r->lanes && !sync && !multi;
   const int buf = r->cur_buf < 0 ? 0 : flip ? r->cur_buf ^ 1 : r->cur_buf;
   if (buf) lw[3] |= r->cbuf1_off & RT_LW_CBUF_MASK;
   if (accum_k)
@@ -1420,6 +1544,7 @@ int render_start(rt_renderer_h r, bool sync, uint32_t accum_k) {
   const bool bvh = mode == 0 && (f & RT_RENDER_BVH_WALK) && !r->deep && (r->arg.flags & RT_FLAG_BVH4H) &&
                    r->krnl_bvh[k];
   vx_buffer_h img = bvh ? r->krnl_bvh[k] : r->krnl[mode][k];
+  if (multi) img = r->krnl_lights[k];  // (set_lights admits plain shadow frames only: mode 0, no tail)
   // a scene with an ordered tail: head traced, tail folded, one launch
   if (mode == 0 && !r->sc->tail_prims.empty()) img = r->krnl_om;
   return start(img) ? 0 : fail("vx_start failed");

@@ -56,9 +56,43 @@ struct SetupScratch {
   }
 };
 
+// One set of light-space shadow lists (device_setup.cpp slist_args .. settle_lists work on a
+// set): the index and entry buffers, the entry capacity, the light they were built for and
+// what became of them.  Set 0 is the renderer's own state (sidx / slist, su.scap, sl_*: the
+// single light of every path before rt_renderer_set_lights), named through this view; the sets
+// of a several-light frame are LightSet::own.
+struct ListSet {
+  vx_buffer_h *sidx, *slist;
+  uint64_t *sidx_addr, *slist_addr;
+  uint32_t* cap;       // entry capacity of slist (and of the chain's stmp scratch while it builds)
+  float* light;        // the light the lists were built for
+  bool *built, *rejected;
+  uint64_t* entries;
+};
+// a light of rt_renderer_set_lights with the storage of its set
+struct LightSet {
+  vx_buffer_h sidx = nullptr, slist = nullptr;
+  uint64_t sidx_addr = 0, slist_addr = 0;
+  uint32_t cap = 0;
+  float light[3] = {0, 0, 0};
+  bool built = false, rejected = false;
+  uint64_t entries = 0;
+  ListSet set() { return ListSet{&sidx, &slist, &sidx_addr, &slist_addr, &cap, light, &built, &rejected, &entries}; }
+};
+
 struct rt_renderer {
   rt_scene* sc = nullptr;
   vx_device_h dev = nullptr;
+  // several lights (vx_rt.h rt_renderer_set_lights): rt_lights / rt_lights_stats, loaded by the
+  // first set_lights; the lights' list sets (kept across calls: their buffers only grow) and
+  // the number in use -- 0: one light, the renderer's own state, every path as before
+  vx_buffer_h krnl_lights[2] = {};
+  std::vector<LightSet> lsets;
+  uint32_t nlights = 0;
+  ListSet set0() {
+    return ListSet{&sidx, &slist, &arg.sidx_addr, &arg.slist_addr, &su.scap, sl_light, &sl_built, &sl_rejected,
+                   &sl_entries};
+  }
   // kernel images [mode][instrumented]: mode 0 = primary+shadow (BVH),
   // 1 = path trace, 2 = flat list, 3 = raster (no instrumented image)
   vx_buffer_h krnl[4][2] = {};
@@ -196,11 +230,17 @@ struct rt_renderer {
                            &blist, &bidx, &cdesc, &sidx, &slist, &krnl_pq[0][0], &krnl_pq[0][1],
                            &krnl_pq[1][0], &krnl_pq[1][1], &pathq, &pathq_ctr,
                            &krnl_bvh[0], &krnl_bvh[1], &sah_krnl, &krnl_om, &oidx, &olist, &ovtris,
-                           &krnl_accum, &accum};
+                           &krnl_accum, &accum, &krnl_lights[0], &krnl_lights[1]};
     for (auto* b : bufs) {
       if (*b) vx_mem_free(*b);
       *b = nullptr;
     }
+    for (LightSet& l : lsets)
+      for (vx_buffer_h* b : {&l.sidx, &l.slist})
+        if (*b) {
+          vx_mem_free(*b);
+          *b = nullptr;
+        }
     su.release();
     if (dev) vx_dev_close(dev);
   }
@@ -255,6 +295,11 @@ int queue_lists(rt_renderer* r, uint32_t* launches);
 // read the status of lists queued by set_light (waits for the device): their
 // size, an overflow refill, r->sl_built
 int settle_lists(rt_renderer* r);
+// rt_renderer_set_lights: one list set per light (r->lsets[0 .. n)), each by the chain
+// queue_lists runs for set 0 -- the chains share the setup's scratch and are stream-ordered;
+// each set's status is read (an overflow refilled at its exact size) before the next chain
+// starts, so the call waits for the device.  lists false: no set is built (slist_on 0).
+int build_light_sets(rt_renderer* r, const float (*lights)[3], uint32_t n, bool lists, uint32_t* launches);
 // whether lists with this longest list and this many entries are built
 // (RT_BLIST_MAX_LIST, the device sort's limit; env RT_BLIST_MAX_ENTRIES,
 // default 16 M entries = 512 MiB of list and sort buffers)

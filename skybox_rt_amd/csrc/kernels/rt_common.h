@@ -266,6 +266,44 @@ typedef struct {
   uint32_t pad[3];
 } rt_tier_arg_t;
 #define RT_TIER_ARG_OFFSET (sizeof(rt_kernel_arg_t) + sizeof(rt_accum_arg_t))
+// The light table of a frame lit by several point lights (rt_kernel.hip RT_LIGHTS, images
+// rt_lights / rt_lights_stats; vx_rt.h rt_renderer_set_lights), behind the three above, which
+// stay where they are: per light its position and its own light-space shadow lists (slist_on 0:
+// that light's shadow rays walk the BVH); every set is built at slist_n cells per face side.
+#define RT_MAX_LIGHTS 16u
+typedef struct {
+  float light[3];
+  uint32_t slist_on;
+  uint64_t sidx_addr;
+  uint64_t slist_addr;
+} rt_light_t;
+typedef struct {
+  uint32_t count, slist_n, pad[2];
+  rt_light_t l[RT_MAX_LIGHTS];
+} rt_lights_arg_t;
+#define RT_LIGHTS_ARG_OFFSET (RT_TIER_ARG_OFFSET + sizeof(rt_tier_arg_t))
+// The pixel of a shadow ray that `occluded` of its k lights (1 <= k <= RT_MAX_LIGHTS) do not
+// see: per channel the rounded mean of the k single-light values, c for a light that sees it
+// and c >> 1 (shadowed()) for one that does not -- sum = (k - o) * c + o * (c >> 1), mean =
+// (2 * sum + k) / (2 * k) in integer division, the accumulation resolve on {sums, k}; the alpha
+// byte is c's.  The division is a multiplication by m = ceil(2^20 / d), d = 2k <= 32: with
+// e = m * d - 2^20 in [0, d), n * m / 2^20 = n / d + n * e / (d * 2^20), and the second term
+// stays below 1 / d -- so the floor is floor(n / d) -- while n * e < 2^20; n = 2 * sum + k <=
+// 2 * 16 * 255 + 16 = 8176 and e <= 31 give n * e <= 253 456.  n * m < 2^13 * 2^19 fits 32 bits.
+// The kernel and the host (rt_lights_resolve) share this text.
+#if defined(__HIPCC__)
+__host__ __device__
+#endif
+static inline uint32_t rt_lights_mix(uint32_t argb, uint32_t occluded, uint32_t k) {
+  const uint32_t d = 2u * k, m = (0x100000u + d - 1u) / d;
+  uint32_t out = argb & 0xff000000u;
+  for (int s = 0; s <= 16; s += 8) {
+    const uint32_t c = (argb >> s) & 0xffu;
+    const uint32_t sum = (k - occluded) * c + occluded * (c >> 1);
+    out |= (((2u * sum + k) * m) >> 20) << s;
+  }
+  return out;
+}
 // padding entries after the last tail list (the first tail pid): the fold
 // loads the entry two ahead and the record one ahead of the one it tests
 #define RT_OLIST_PAD 2u

@@ -28,7 +28,8 @@
 // without the list code paths), rt_kernel_deep (every
 // BVH layout: per-lane walks with a 32-entry LDS stack for the layouts the
 // packet walk does not read), rt_flat (RT_FLAT: BASELINE config 2, the flat
-// geometry list, no BVH).
+// geometry list, no BVH), rt_lights (RT_LIGHTS: rt_kernel lit by the lights
+// of a table, every queued shadow ray against each of them in one drain).
 #include <hip/hip_runtime.h>
 
 #ifndef RT_BLOCK_THREADS
@@ -47,6 +48,9 @@
 // background tier (bg_tier below)
 #ifndef RT_BG_TIER
 #define RT_BG_TIER 0
+#endif
+#if RT_LIGHTS && (RT_FLAT || RT_PATHQ || RT_BVH_WALK || !RT_ONLY_BVH4H)
+#error "RT_LIGHTS is for the primary+shadow list image on the binary16 BVH4"
 #endif
 #if RT_BG_TIER && (RT_FLAT || RT_PATHQ || RT_BVH_WALK || !RT_CHUNK_DESC)
 #error "RT_BG_TIER is for the primary+shadow list image with the chunk descriptor table"
@@ -213,6 +217,33 @@ __device__ __forceinline__ void shadow_drain(bool final, const Scene& S, WaveLds
     const bool active = lane < take;
     const uint32_t slot = base + lane;  // < RT_QUEUE for every lane
     const uint32_t xy = w.q_xy[slot];
+#if RT_LIGHTS
+    // the packet against every light of the table in turn (a wave-uniform loop: the table is
+    // read through the scalar cache); a lane some light does not see stays in the packet for
+    // the lights after it, so each light's packet holds the rays of that light's own frame.
+    // o = the lights that do not see the lane's ray: its pixel is the rounded mean of the
+    // single-light frames' values (rt_common.h rt_lights_mix), stored once
+    Ray p;
+    primary_dir(S, xy & 0xffffu, xy >> 16, p);
+    const float th = w.q_t[slot];
+    const int32_t pid = w.q_pid[slot];
+    const auto* LA = lights_args(S);
+    const uint32_t nl = LA->count, sn = LA->slist_n;
+    uint32_t o = 0;
+    for (uint32_t i = 0; i < nl; ++i) {
+      const float L[3] = {LA->l[i].light[0], LA->l[i].light[1], LA->l[i].light[2]};
+      Ray s;
+      shadow_ray(S, p, th, s, L);
+      cnt.shadow += active;
+      const bool occ = LA->l[i].slist_on ? occluded_list(S, s, active, pid, cnt, (uint32_t)LA->l[i].sidx_addr,
+                                                         (uint32_t)LA->l[i].slist_addr, sn)
+                                         : occluded_packet(walk_scene(S), s, active, pid, 1.0f, cnt);
+      o += occ ? 1u : 0u;
+    }
+    cnt.occluded += o;
+    if (active) store_out(S, w.q_out[slot], rt_lights_mix(w.q_color[slot], o, nl));
+    (void)tie_high;
+#else
     Ray p, s;
     primary_dir(S, xy & 0xffffu, xy >> 16, p);
     shadow_ray(S, p, w.q_t[slot], s);
@@ -231,6 +262,7 @@ __device__ __forceinline__ void shadow_drain(bool final, const Scene& S, WaveLds
       color = shadowed(color);
     }
     if (active) store_out(S, w.q_out[slot], color);
+#endif
     n = base;
   }
   __builtin_amdgcn_wave_barrier();

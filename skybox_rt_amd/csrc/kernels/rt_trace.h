@@ -58,6 +58,15 @@
 #ifndef RT_CHUNK_DESC
 #define RT_CHUNK_DESC 0
 #endif
+//   RT_LIGHTS      images rt_lights / rt_lights_stats: a frame lit by the lights
+//                  of the table behind the argument block (rt_common.h
+//                  rt_lights_arg_t), every queued shadow ray tested against
+//                  each of them in one drain (rt_kernel.hip shadow_drain);
+//                  shadow_ray and occluded_list then take the light and its
+//                  list bases as parameters
+#ifndef RT_LIGHTS
+#define RT_LIGHTS 0
+#endif
 
 namespace rtk {
 
@@ -830,6 +839,16 @@ __device__ __forceinline__ uint32_t slist_cell(const Ray& s, uint32_t N) {
 __device__ __forceinline__ float slist_limit(const Ray& s) {
   return (s.d[0] * s.d[0] + s.d[1] * s.d[1] + s.d[2] * s.d[2]) * 1.001f;
 }
+#if RT_LIGHTS
+// (the lists of one light of the table: their index and entries, at n cells per face side)
+__device__ __forceinline__ bool occluded_list(const Scene& S, const Ray& s, bool act, int32_t skip,
+                                              Counters& cnt, uint32_t sidx, uint32_t slist, uint32_t slist_n) {
+  if (!act) return false;
+  const uint32_t cell = slist_cell(s, slist_n);
+  const uint32_t off = S.A.ld_u32(sidx + 8u * cell), n = S.A.ld_u32(sidx + 8u * cell + 4u);
+  const float lim = slist_limit(s);
+  uint32_t o = slist + 48u * off;
+#else
 __device__ __forceinline__ bool occluded_list(const Scene& S, const Ray& s, bool act, int32_t skip,
                                               Counters& cnt) {
   if (!act) return false;
@@ -837,6 +856,7 @@ __device__ __forceinline__ bool occluded_list(const Scene& S, const Ray& s, bool
   const uint32_t off = S.A.ld_u32(S.sidx + 8u * cell), n = S.A.ld_u32(S.sidx + 8u * cell + 4u);
   const float lim = slist_limit(s);
   uint32_t o = S.slist + 48u * off;
+#endif
   for (uint32_t q = 0; q < n; q += 2, o += 96u) {
     float4 t[6];
 #pragma unroll
@@ -1801,6 +1821,24 @@ __device__ __forceinline__ void primary_dir(const Scene& S, uint32_t x, uint32_t
 }
 
 // shadow segment from the (eye-ward nudged) hit point to the light
+#if RT_LIGHTS
+// (to one light of the table: the origin does not depend on it)
+__device__ __forceinline__ void shadow_ray(const Scene& S, const Ray& p, float th, Ray& s, const float light[3]) {
+  const float tt = th * 0.999755859375f;  // origin pulled toward the eye by 2^-12 of t
+  s.o[0] = p.d[0] * tt; s.o[1] = p.d[1] * tt; s.o[2] = p.d[2] * tt;
+  s.d[0] = light[0] - s.o[0];
+  s.d[1] = light[1] - s.o[1];
+  s.d[2] = light[2] - s.o[2];
+  ray_setup(s);
+}
+// the light table, in the argument buffer behind the tier's area: read where used, through the
+// scalar cache (wave-uniform address: a light's fields live in SGPRs)
+__device__ __forceinline__ const __attribute__((address_space(4))) rt_lights_arg_t* lights_args(const Scene& S) {
+  uint64_t p = S.argp + RT_LIGHTS_ARG_OFFSET;
+  asm volatile("" : "+s"(p));
+  return (const __attribute__((address_space(4))) rt_lights_arg_t*)p;
+}
+#else
 __device__ __forceinline__ void shadow_ray(const Scene& S, const Ray& p, float th, Ray& s) {
   const float tt = th * 0.999755859375f;  // origin pulled toward the eye by 2^-12 of t
   s.o[0] = p.d[0] * tt; s.o[1] = p.d[1] * tt; s.o[2] = p.d[2] * tt;
@@ -1809,6 +1847,7 @@ __device__ __forceinline__ void shadow_ray(const Scene& S, const Ray& p, float t
   s.d[2] = S.light[2] - s.o[2];
   ray_setup(s);
 }
+#endif
 
 // Path tracing in two kernels (BASELINE config 4's wave64 active-ray
 // compaction): the first pass (pt_primary, rt_kernel.hip built

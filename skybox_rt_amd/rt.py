@@ -76,6 +76,13 @@ class SetupStats(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_ if n != "pad"}
 
 
+class LightInfo(C.Structure):
+    _fields_ = [("light", C.c_float * 3), ("slist_on", C.c_uint32), ("slist_entries", C.c_uint64)]
+
+
+RT_MAX_LIGHTS = 16
+
+
 class RenderParams(C.Structure):
     _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("flags", C.c_uint32),
                 ("light", C.c_float * 3), ("clear_color", C.c_uint32),
@@ -157,6 +164,9 @@ def lib():
             "rt_render_accumulate": [vp, u32],
             "rt_renderer_accum_samples": [vp, C.POINTER(u32)],
             "rt_read_accum": [vp, vp, u64],
+            "rt_renderer_set_lights": [vp, vp, u32],
+            "rt_renderer_lights_info": [vp, C.POINTER(LightInfo), u32, C.POINTER(u32)],
+            "rt_renderer_export_light_lists": [vp, u32, u32, vp, u64, C.POINTER(u64)],
         }
         for name, argtypes in sig.items():
             fn = getattr(h, name)
@@ -164,6 +174,8 @@ def lib():
             fn.restype = C.c_int
         h.rt_accum_resolve.argtypes = [C.POINTER(u32), u32]
         h.rt_accum_resolve.restype = u32
+        h.rt_lights_resolve.argtypes = [u32, u32, u32]
+        h.rt_lights_resolve.restype = u32
         h.rt_last_error.restype = C.c_char_p
         h.rt_last_error.argtypes = []
         _h = h
@@ -346,6 +358,38 @@ class Renderer:
         arr = (C.c_float * 3)(*[float(np.float32(x)) for x in light])
         _check(lib().rt_renderer_set_light(self._h, arr), "rt_renderer_set_light")
         self.params.light[:] = [float(np.float32(x)) for x in light]
+
+    # several lights (vx_rt.h rt_renderer_set_lights; images rt_lights / rt_lights_stats)
+    def set_lights(self, lights) -> None:
+        """Light the configured primary + shadow frame by 1..16 point lights
+        (clip x, y, w each): the frames after it are, per pixel and channel,
+        the rounded mean of the single-light frames, traced in one launch --
+        primary visibility and shading once, every shadow ray against each
+        light on that light's own shadow lists.  Builds the lists at once and
+        waits for the device.  set_light() and configure() return to one light."""
+        arr = np.ascontiguousarray(np.asarray(lights, np.float32).reshape(-1, 3))
+        _check(lib().rt_renderer_set_lights(self._h, arr.ctypes.data, arr.shape[0]), "rt_renderer_set_lights")
+        self.params.light[:] = [float(x) for x in arr[0]]
+
+    def lights_info(self) -> list:
+        """The lights in use: per light {light, slist_on, slist_entries}."""
+        out = (LightInfo * RT_MAX_LIGHTS)()
+        n = C.c_uint32()
+        _check(lib().rt_renderer_lights_info(self._h, out, RT_MAX_LIGHTS, C.byref(n)), "rt_renderer_lights_info")
+        return [{"light": tuple(out[i].light), "slist_on": out[i].slist_on,
+                 "slist_entries": out[i].slist_entries} for i in range(n.value)]
+
+    def light_records(self, i: int, name: str) -> np.ndarray:
+        """Light i's shadow-list array ("sidx" or "slist"), as records() gives
+        the single light's."""
+        which, dt, words = RECORDS[name]
+        n = C.c_uint64()
+        _check(lib().rt_renderer_export_light_lists(self._h, int(i), which, None, 0, C.byref(n)),
+               f"rt_renderer_export_light_lists({i}, {name})")
+        out = np.zeros(max(n.value // 4, 1), dt)
+        _check(lib().rt_renderer_export_light_lists(self._h, int(i), which, out.ctypes.data, out.nbytes,
+                                                    C.byref(n)), f"rt_renderer_export_light_lists({i}, {name})")
+        return out[:n.value // 4].reshape(-1, words)
 
     def set_list_policy(self, defer_frames: int) -> None:
         """0: set_light queues the new light's shadow lists at once; n > 0:
@@ -596,6 +640,13 @@ def accum_resolve(rec, alpha_argb: int) -> int:
     resolves to -- alpha_argb's alpha over the rounded means (2 * sum + n) // (2 * n)."""
     arr = (C.c_uint32 * 4)(*[int(v) for v in rec])
     return int(lib().rt_accum_resolve(arr, int(alpha_argb) & 0xFFFFFFFF))
+
+
+def lights_resolve(argb: int, occluded: int, k: int) -> int:
+    """rt_lights_resolve: the pixel of a shadow ray of primary colour argb that
+    `occluded` of its k lights do not see -- per channel (2 * sum + k) // (2 * k),
+    sum = (k - occluded) * c + occluded * (c >> 1); argb's alpha."""
+    return int(lib().rt_lights_resolve(int(argb) & 0xFFFFFFFF, int(occluded), int(k)))
 
 
 def deinterleave_tiles(shards, width: int, height: int) -> np.ndarray:
