@@ -429,6 +429,56 @@ int rt_renderer_export_light_lists(rt_renderer_h r, uint32_t light, uint32_t whi
  * primary colour argb that `occluded` of its k lights do not see */
 uint32_t rt_lights_resolve(uint32_t argb, uint32_t occluded, uint32_t k);
 
+/* Several point lights on a path-traced frame, traced in one launch.  NO
+ * REFERENCE (the reference has neither a path tracer nor a second light).
+ *
+ * A path frame lit by lights L_0 .. L_{n-1} (1 <= n <= RT_MAX_PATH_LIGHTS) is,
+ * per pixel and colour channel, the rounded mean (2 * sum + n) / (2 * n) in
+ * integer division of the n single-light 8-bit RT_RENDER_PATH frames of the
+ * same seed (rt_accum_resolve on {sums, n}; rt_path_lights_resolve), under
+ * the primary colour's alpha; a pixel that starts no path is its primary
+ * colour.  A path's vertices -- primary hit, bounce directions (keyed by
+ * pixel, vertex and seed), albedos, throughput -- do not depend on the
+ * light, so the kernel traces every bounce ray once and at each vertex one
+ * shadow ray per light, on that light's own light-space lists, into one
+ * radiance accumulator per light that takes the single-light frame's own
+ * operations (images pt_lights / pt_lights_accum).  Counters
+ * (RT_RENDER_COUNTERS): primary_rays, geometry_hits and bounce_rays are one
+ * single-light frame's; shadow_rays and occluded are the sums over the n
+ * single-light frames.
+ *
+ * rt_renderer_set_path_lights: valid on a configured RT_RENDER_PATH frame
+ * that rt_renderer_accum_begin would accept -- the one-kernel per-lane form
+ * on the binary16 BVH4, not RT_RENDER_INSTRUMENTED -- whose shadow rays scan
+ * light-space lists (RT_RENDER_COUNTERS, COMPACT and shards as usual).  It
+ * builds one set of lists per light at once, reads each set's status and
+ * uploads the light table: it WAITS FOR THE DEVICE, like a configure.  With
+ * n >= 2 the frames after it (rt_render, rt_render_start) launch pt_lights
+ * and rt_render_accumulate[_start] launch pt_lights_accum, all as ordinary
+ * launches on the image's grid into the framebuffer in use -- no launch
+ * lane, no overlap.  Sample j of an accumulation is then the n-light frame of
+ * seed s0 + j (an 8-bit value per channel); records and the sample cursor
+ * keep their form.  n = 1 is rt_renderer_set_light under list policy 0.
+ * While accumulation is on, the call starts the records over, as
+ * rt_renderer_set_light does.  rt_renderer_set_light and
+ * rt_renderer_configure return to one light; rt_renderer_lights_info and
+ * rt_renderer_export_light_lists report the sets.
+ * -2 (rt_last_error says why) for n outside 1..RT_MAX_PATH_LIGHTS, a
+ * configuration without RT_RENDER_PATH or with RT_RENDER_INSTRUMENTED, one
+ * without light-space lists (RT_RENDER_BVH_WALK, RT_RENDER_HOST_SETUP, env
+ * RT_SHADOW_LISTS=0, a scene without geometry), the two-kernel queue (env
+ * RT_PT_QUEUE=1), a tree the generic (deep) images run, a kernel directory
+ * with a pt_kernel.vxbin of its own and no pt_lights.vxbin /
+ * pt_lights_accum.vxbin, and any light whose lists do not fit (there is no
+ * BVH fallback per light).  After a refusal the renderer is lit by its single
+ * light, as after rt_renderer_set_light. */
+#define RT_MAX_PATH_LIGHTS 8u
+int rt_renderer_set_path_lights(rt_renderer_h r, const float (*lights)[3], uint32_t n);
+/* the host restatement of the device mean: the pixel whose k single-light
+ * values sum to sums[0..2] = {R, G, B}, under alpha_argb's alpha byte; k
+ * outside 1..RT_MAX_PATH_LIGHTS or a sum above 255 * k: the alpha byte alone */
+uint32_t rt_path_lights_resolve(const uint32_t sums[3], uint32_t k, uint32_t alpha_argb);
+
 /* Read back one per-resolution record array of the current configuration
  * (layouts: kernels/rt_common.h; NO REFERENCE).  out NULL = size query
  * (*size = bytes). */

@@ -18,7 +18,8 @@
 // RASTER_TILE_LOGSIZE 5 the RT path bins at render through the draw3d raster
 // pipeline instead, which is what draw3d itself runs.  Extensions: -S shadow
 // rays, -L x,y,w light, -M x,y,w one more light (repeatable: with -S the
-// frame is lit by the light of -L and every -M, rt_renderer_set_lights), -P N path tracing with N bounces, -F flat triangle
+// frame is lit by the light of -L and every -M, rt_renderer_set_lights; with -P and no -S the path frame is,
+// rt_renderer_set_path_lights, also under -A), -P N path tracing with N bounces, -F flat triangle
 // list, -R raster pipeline, -n N repeat launches, -B lbvh|sah device BVH
 // build, -H host-loop setup, -O load the scene with RT_SCENE_OM_LAYERS (a
 // scene the RT path cannot trace as a whole renders on the RT path all the
@@ -88,7 +89,7 @@ void usage() {
   std::printf("Vortex 3D Rendering Test (MI355X).\n"
               "Usage: [-t trace] [-s startdraw] [-e enddraw] [-o output] [-r reference] [-w width] "
               "[-h height] [-x s/w rast] [-y s/w om] [-u s/w tex] [-k tilelogsize]\n"
-              "       [-S shadows] [-L x,y,w] [-M x,y,w one more light, repeatable] [-n repeat] [-R raster | -P bounces | -F flat] "
+              "       [-S shadows] [-L x,y,w] [-M x,y,w one more light, repeatable: with -S or -P] [-n repeat] [-R raster | -P bounces | -F flat] "
               "[-G rank,ranks [-I idfile]] [-B lbvh|sah device BVH build] [-H host setup]\n"
               "       [-O trace the head, fold blended / stencil / masked drawcalls (RT_SCENE_OM_LAYERS)]\n"
               "       [-A samples: with -P, accumulate that many samples per pixel on the device and "
@@ -161,8 +162,15 @@ int main(int argc, char** argv) {
     std::printf("Tile log size %d: rendering through the draw3d raster pipeline\n", tile_log);
     raster = true;
   }
-  if (!more_lights.empty() && (!shadows || more_lights.size() + 1 > RT_MAX_LIGHTS)) {
-    std::printf("Error: -M x,y,w needs -S (shadow rays), at most %u lights in all\n", RT_MAX_LIGHTS);
+  // (-S decides when both are given: -M with -S behaves as without -P)
+  const bool path_lights = !more_lights.empty() && !shadows && bounces >= 0;
+  if (path_lights && more_lights.size() + 1 > RT_MAX_PATH_LIGHTS) {
+    std::printf("Error: -M x,y,w with -P bounces: at most %u lights in all\n", RT_MAX_PATH_LIGHTS);
+    return 1;
+  }
+  if (!more_lights.empty() && !path_lights && (!shadows || more_lights.size() + 1 > RT_MAX_LIGHTS)) {
+    std::printf("Error: -M x,y,w needs -S (shadow rays, at most %u lights in all) or -P bounces (at most %u)\n",
+                RT_MAX_LIGHTS, RT_MAX_PATH_LIGHTS);
     return 1;
   }
   if (accum_samples && (bounces < 0 || rank >= 0)) {
@@ -269,7 +277,8 @@ int main(int argc, char** argv) {
     std::vector<float> ls(light, light + 3);
     for (const auto& m : more_lights) ls.insert(ls.end(), m.begin(), m.end());
     const uint32_t nl = (uint32_t)more_lights.size() + 1u;
-    RT_CHECK(rt_renderer_set_lights(r, reinterpret_cast<const float(*)[3]>(ls.data()), nl));
+    const auto* lp = reinterpret_cast<const float(*)[3]>(ls.data());
+    RT_CHECK(path_lights ? rt_renderer_set_path_lights(r, lp, nl) : rt_renderer_set_lights(r, lp, nl));
     std::printf("Lights: %u, traced in one launch\n", nl);
   }
   double total = 0.0;

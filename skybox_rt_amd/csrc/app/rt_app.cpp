@@ -686,6 +686,100 @@ uint32_t rt_lights_resolve(uint32_t argb, uint32_t occluded, uint32_t k) {
   return rt_lights_mix(argb, occluded, k);
 }
 
+// ---- several lights on a path frame (vx_rt.h; NO REFERENCE) -----------------
+
+int rt_renderer_set_path_lights(rt_renderer_h r, const float (*lights)[3], uint32_t n) {
+  if (!r) return fail("null argument");
+  if (!r->configured) return fail("renderer not configured");
+  // whatever becomes of the call, the frames after it are not the ones before: a refusal
+  // leaves the single light (as after rt_renderer_set_light), and accumulated samples start over
+  r->nlights = 0;
+  if (r->accum_on) {
+    r->accum_reset = true;
+    r->accum_n = 0;
+  }
+  if (n < 1 || n > RT_MAX_PATH_LIGHTS) return fail("rt_renderer_set_path_lights: 1 to 8 lights", -2);
+  if (!lights) return fail("null argument");
+  const uint32_t f = r->params.flags;
+  if (!(f & RT_RENDER_PATH) || (f & (RT_RENDER_FLAT | RT_RENDER_RASTER)))
+    return fail("rt_renderer_set_path_lights: not an RT_RENDER_PATH configuration", -2);
+  if (f & RT_RENDER_INSTRUMENTED)
+    return fail("rt_renderer_set_path_lights: no instrumented several-light image (RT_RENDER_INSTRUMENTED)", -2);
+  if (r->pq)
+    return fail("rt_renderer_set_path_lights: the two-kernel path queue (RT_PT_QUEUE=1) takes one light", -2);
+  if (!r->sl_mode)
+    return fail("rt_renderer_set_path_lights: this configuration's shadow rays scan no light-space lists "
+                "(RT_RENDER_BVH_WALK, RT_RENDER_HOST_SETUP, RT_SHADOW_LISTS=0, no geometry)", -2);
+  if (r->deep || !(r->arg.flags & RT_FLAG_BVH4H))
+    return fail("rt_renderer_set_path_lights: pt_lights walks the binary16 BVH4 only; this tree runs the generic "
+                "(deep) images", -2);
+  if (!r->set_words) return fail("rt_renderer_set_path_lights: the driver passes no launch words", -2);
+  if (!r->krnl_plights[0]) {
+    // next to the pt_kernel.vxbin in use: the kernel directory's when it holds one (a directory
+    // with a path tracer of its own and no pt_lights images, e.g. pt_compact, is refused)
+    std::string dir = r->kdir;
+    if (FILE* fk = std::fopen((dir + "/pt_kernel.vxbin").c_str(), "rb")) std::fclose(fk);
+    else dir = lib_dir();
+    const char* names[2] = {"pt_lights.vxbin", "pt_lights_accum.vxbin"};
+    for (int i = 0; i < 2; ++i)
+      if (FILE* fa = std::fopen((dir + "/" + names[i]).c_str(), "rb")) std::fclose(fa);
+      else
+        return fail("rt_renderer_set_path_lights: no " + std::string(names[i]) + " next to " + dir +
+                    "/pt_kernel.vxbin", -2);
+    for (int i = 0; i < 2; ++i)
+      if (vx_upload_kernel_file(r->dev, (dir + "/" + names[i]).c_str(), &r->krnl_plights[i]) != 0) {
+        for (int j = 0; j <= i; ++j) {
+          if (r->krnl_plights[j]) vx_mem_free(r->krnl_plights[j]);
+          r->krnl_plights[j] = nullptr;
+        }
+        return fail("cannot upload kernel " + dir + "/" + names[i]);
+      }
+  }
+  if (n == 1) {
+    // one light: rt_renderer_set_light with its lists queued at once
+    const uint32_t defer = r->sl_defer;
+    r->sl_defer = 0;
+    const int e = rt_renderer_set_light(r, lights[0]);
+    r->sl_defer = defer;
+    if (e != 0) return e;
+    return rtapp::settle_lists(r);
+  }
+  // a list set per light, each chain behind the frames in flight; then the table, in stream
+  // order ahead of every frame started after it
+  uint32_t launches = 0;
+  if (rtapp::build_light_sets(r, lights, n, true, &launches) != 0) return -1;
+  rt_lights_arg_t la{};
+  la.count = n;
+  la.slist_n = r->arg.slist_n;
+  for (uint32_t i = 0; i < n; ++i) {
+    const LightSet& l = r->lsets[i];
+    if (!l.built)
+      return fail("rt_renderer_set_path_lights: the light-space lists of light " + std::to_string(i) +
+                  " do not fit (pt_lights has no BVH shadow walk)", -2);
+    std::memcpy(la.l[i].light, l.light, sizeof(l.light));
+    la.l[i].slist_on = 1u;
+    la.l[i].sidx_addr = l.sidx_addr;
+    la.l[i].slist_addr = l.slist_addr;
+    if (((l.sidx_addr | l.slist_addr) >> 32) != 0) return fail("light-space lists above 4 GiB");
+  }
+  if (r->copy_async ? r->copy_async(r->args, &la, RT_LIGHTS_ARG_OFFSET, sizeof(la)) != 0
+                    : vx_copy_to_dev(r->args, &la, RT_LIGHTS_ARG_OFFSET, sizeof(la)) != 0)
+    return fail("light table upload failed");
+  if (vx_ready_wait(r->dev, VX_MAX_TIMEOUT) != 0) return fail("vx_ready_wait failed");
+  r->nlights = n;
+  r->lane_break = true;
+  return 0;
+}
+
+uint32_t rt_path_lights_resolve(const uint32_t sums[3], uint32_t k, uint32_t alpha_argb) {
+  uint32_t c = alpha_argb & 0xff000000u;
+  if (!sums || k < 1 || k > RT_MAX_PATH_LIGHTS) return c;
+  for (int i = 0; i < 3; ++i)
+    if (sums[i] > 255u * k) return c;
+  for (int i = 0; i < 3; ++i) c |= rt_path_lights_mean(sums[i], k) << (16 - 8 * i);
+  return c;
+}
+
 int rt_renderer_export_records(rt_renderer_h r, uint32_t which, void* out, uint64_t bytes,
                                uint64_t* size) {
   if (!r || !r->configured) return fail("renderer not configured");
@@ -1487,7 +1581,8 @@ int render_start(rt_renderer_h r, bool sync, uint32_t accum_k) {
   // for a light that stays, the switch to the BVH walk) in its launch words:
   // rt_renderer_set_light queues no copy
   // (a frame of several lights reads them from its table: neither launch-word bit)
-  const bool multi = r->nlights >= 2 && !accum_k;
+  // (nor does a path frame of several lights, rt_renderer_set_path_lights, accumulating or not)
+  const bool multi = r->nlights >= 2 && (mode == 1 || !accum_k);
   uint32_t lw[4] = {0, 0, 0, 0};
   if (r->set_words && !multi) {
     std::memcpy(lw, r->arg.light, sizeof(r->arg.light));
@@ -1531,7 +1626,9 @@ int render_start(rt_renderer_h r, bool sync, uint32_t accum_k) {
   if (r->set_counters &&
       r->set_counters(r->dev, (f & (RT_RENDER_COUNTERS | RT_RENDER_INSTRUMENTED)) ? 1 : 0) != 0)
     return fail("vx_hip_set_counters failed");
-  if (accum_k) return start(r->krnl_accum) ? 0 : fail("vx_start failed");
+  if (accum_k) return start(multi ? r->krnl_plights[1] : r->krnl_accum) ? 0 : fail("vx_start failed");
+  // a path frame of several lights: pt_lights (set_path_lights admits the one-kernel form only)
+  if (multi && mode == 1) return start(r->krnl_plights[0]) ? 0 : fail("vx_start failed");
   // a frame of the two-kernel path tracer is one launch group of 2
   if (mode == 1 && r->pq) {
     if (r->launch_group(r->dev, 2) != 0) return fail("vx_hip_launch_group failed");

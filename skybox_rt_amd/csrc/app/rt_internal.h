@@ -87,6 +87,9 @@ struct rt_renderer {
   // first set_lights; the lights' list sets (kept across calls: their buffers only grow) and
   // the number in use -- 0: one light, the renderer's own state, every path as before
   vx_buffer_h krnl_lights[2] = {};
+  // a path frame under several lights (rt_renderer_set_path_lights): pt_lights, pt_lights_accum,
+  // loaded by the first call; lsets and nlights as above
+  vx_buffer_h krnl_plights[2] = {};
   std::vector<LightSet> lsets;
   uint32_t nlights = 0;
   ListSet set0() {
@@ -230,7 +233,8 @@ struct rt_renderer {
                            &blist, &bidx, &cdesc, &sidx, &slist, &krnl_pq[0][0], &krnl_pq[0][1],
                            &krnl_pq[1][0], &krnl_pq[1][1], &pathq, &pathq_ctr,
                            &krnl_bvh[0], &krnl_bvh[1], &sah_krnl, &krnl_om, &oidx, &olist, &ovtris,
-                           &krnl_accum, &accum, &krnl_lights[0], &krnl_lights[1]};
+                           &krnl_accum, &accum, &krnl_lights[0], &krnl_lights[1],
+                           &krnl_plights[0], &krnl_plights[1]};
     for (auto* b : bufs) {
       if (*b) vx_mem_free(*b);
       *b = nullptr;

@@ -19,7 +19,10 @@
 // lane, the 32-pixel waves of geometry tiles with paired shadow / bounce
 // lanes; pt_compact (PT_MODE 0) keeps a 256-thread workgroup's live paths in
 // an LDS queue and after each vertex appends the survivors to the other
-// queue at ballot + mbcnt slots (wave64 compaction).
+// queue at ballot + mbcnt slots (wave64 compaction).  Built from the per-lane
+// form as well: pt_accum (PT_ACCUM, k samples a launch into per-pixel sums),
+// pt_lights / pt_lights_accum (PT_LIGHTS: one shadow ray per light of a table
+// at every vertex, the pixel the rounded mean of the single-light frames).
 #include <hip/hip_runtime.h>
 
 #ifndef PT_MODE
@@ -31,6 +34,24 @@
 #define PT_BLOCK 64
 #endif
 #define VX_BLOCK_THREADS PT_BLOCK  // vx_spawn.h: the workgroup size as a constant
+// PT_LIGHTS (images pt_lights, and with PT_ACCUM pt_lights_accum): the frame lit by the lights
+// of the table behind the argument block (rt_common.h rt_lights_arg_t, at most
+// RT_MAX_PATH_LIGHTS of them, every one with light-space lists).  A path's vertices do not
+// depend on the light, so P, the normal, the bounce ray, path_hit and T are computed once per
+// vertex; only the shadow ray and its T * cos term run per light, into one radiance
+// accumulator per light -- each takes the single-light frame's own operation sequence, so the
+// pixel, the rounded mean of the lights' 8-bit values, equals the mean of the single-light
+// frames bit for bit.  The accumulators live in LDS, a column per lane next to the stack's.
+// Only the list-scan forms: no paired-vertex code, no BVH shadow walk (the host refuses a
+// light without lists).
+#ifdef PT_LIGHTS
+#if PT_MODE != 1
+#error "PT_LIGHTS is for the one-kernel per-lane form (PT_MODE 1)"
+#endif
+#define RT_LIGHTS 1  // rt_trace.h: lights_args, occluded_list / occluded_list_coop on a light's own lists
+#undef PT_PAIR
+#define PT_PAIR 0
+#endif
 #include "rt_trace.h"
 
 // PT_MODE 1 (default image pt_kernel): every lane runs its own path to the
@@ -138,6 +159,11 @@ struct PathQueue {
 
 struct PtLds {
   int32_t stack[kWaves][RT_STACK_ROWS][64];
+#ifdef PT_LIGHTS
+  // radiance of light i, channel k, of lane l's path: lacc[w][3 * i + k][l] (a conflict-free
+  // column per lane, as the stack's)
+  float lacc[kWaves][3 * RT_MAX_PATH_LIGHTS][64];
+#endif
 #if PT_MODE == 0
   PathQueue q[2];
   uint32_t n[2];
@@ -211,6 +237,9 @@ struct PathState {
 #ifdef PT_ACCUM
   uint32_t seed;  // this sample's RNG seed (arg seed + the record's sample cursor + j)
 #endif
+#ifdef PT_LIGHTS
+  float* lacc;    // this lane's column of the per-light radiance accumulators (L is unused)
+#endif
 };
 // the bounce RNG's seed: the configured one, or (image pt_accum) the sample's
 #ifdef PT_ACCUM
@@ -220,6 +249,30 @@ struct PathState {
 #endif
 // (the pair form carrying the vertex normal from the hit instead of loading
 // the triangle again at the next vertex measured no gain, r05)
+
+#ifdef PT_LIGHTS
+// the lights of the table (the host sets 2 .. RT_MAX_PATH_LIGHTS; never past the accumulators)
+__device__ __forceinline__ uint32_t lights_count(const Scene& S) {
+  return min(lights_args(S)->count, RT_MAX_PATH_LIGHTS);
+}
+// the per-light accumulators of a path that starts: L_i = 0 for every light of the table
+__device__ __forceinline__ void lights_zero(const Scene& S, PathState& st) {
+  const uint32_t nl = lights_count(S);
+  for (uint32_t i = 0; i < 3u * nl; ++i) st.lacc[64u * i] = 0.0f;
+}
+// the finished path's colour: per channel the rounded mean of the lights' to8(L_i)
+// (rt_common.h rt_path_lights_mean), packed as the pixel's low 24 bits
+__device__ __forceinline__ uint32_t lights_rgb(const Scene& S, const PathState& st) {
+  const uint32_t nl = lights_count(S);
+  uint32_t sum[3] = {0u, 0u, 0u};
+  for (uint32_t i = 0; i < nl; ++i) {
+#pragma unroll
+    for (int k = 0; k < 3; ++k) sum[k] += to8(st.lacc[64u * (3u * i + (uint32_t)k)]);
+  }
+  return (rt_path_lights_mean(sum[0], nl) << 16) | (rt_path_lights_mean(sum[1], nl) << 8) |
+         rt_path_lights_mean(sum[2], nl);
+}
+#endif
 
 // The next vertex of a path whose bounce ray b from P hit triangle np at t:
 // albedo = the draw3d shader at the hit's MT barycentrics, T *= albedo
@@ -289,6 +342,42 @@ __device__ __forceinline__ bool path_step(const Scene& S, int32_t* stack, PathSt
   const float tt = st.t * 0.999755859375f;
 #pragma unroll
   for (int k = 0; k < 3; ++k) P[k] = fmaf(st.d[k], tt, st.o[k]);
+#ifdef PT_LIGHTS
+  // direct light: a shadow segment P -> light per light of the table, each on that light's
+  // own lists (a wave-uniform loop: the table is read through the scalar cache); light i's
+  // term goes to its own accumulator, the single-light frame's fmaf
+  const auto* LA = lights_args(S);
+  const uint32_t nl = lights_count(S), sn = LA->slist_n;
+  const uint64_t c0 = PT_CYC();
+  for (uint32_t i = 0; i < nl; ++i) {
+    Ray s;
+    s.o[0] = P[0]; s.o[1] = P[1]; s.o[2] = P[2];
+    s.d[0] = LA->l[i].light[0] - P[0];
+    s.d[1] = LA->l[i].light[1] - P[1];
+    s.d[2] = LA->l[i].light[2] - P[2];
+    ray_setup(s);
+    cnt.shadow += act ? one : 0u;
+    const uint32_t sidx = (uint32_t)LA->l[i].sidx_addr, slist = (uint32_t)LA->l[i].slist_addr;
+    const bool occ = CO == 1 ? occluded_list_coop(S, s, act, st.pid, hi, cnt, sidx, slist, sn)
+                             : occluded_list(S, s, act, st.pid, cnt, sidx, slist, sn);
+    cnt.occluded += occ ? one : 0u;
+    if (act && !occ) {
+      const float cosl = dot3(nrm, s.d) / sqrtf(dot3(s.d, s.d));
+      if (cosl > 0.0f) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+          float* l = st.lacc + 64u * (3u * i + (uint32_t)k);
+          *l = fmaf(st.T[k], cosl, *l);
+        }
+      }
+    }
+  }
+  const uint64_t c1 = PT_CYC();
+  if (CO) {
+    PT_ACC(4, c1 - c0);  // cycles in the shadow-list scans
+    PT_ACC(5, 1);        // vertex steps
+  }
+#else
   // direct light: shadow segment P -> light
   Ray s;
   s.o[0] = P[0]; s.o[1] = P[1]; s.o[2] = P[2];
@@ -316,6 +405,7 @@ __device__ __forceinline__ bool path_step(const Scene& S, int32_t* stack, PathSt
       for (int k = 0; k < 3; ++k) st.L[k] = fmaf(st.T[k], cosl, st.L[k]);
     }
   }
+#endif  // PT_LIGHTS
   bool alive = act && v < S.bounces;
   int32_t np = -1;
   float nt = 0.0f;
@@ -328,8 +418,18 @@ __device__ __forceinline__ bool path_step(const Scene& S, int32_t* stack, PathSt
     np = CO == 1 ? trace_coop(S, b, st.pid, tie_high, &nt, stack, hi, cnt)
                  : trace<false>(S, b, 0.0f, INFINITY, st.pid, tie_high, &nt, stack, cnt);
     if (np < 0) {
+#ifdef PT_LIGHTS
+      for (uint32_t i = 0; i < nl; ++i) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+          float* l = st.lacc + 64u * (3u * i + (uint32_t)k);
+          *l = fmaf(st.T[k], PT_SKY, *l);
+        }
+      }
+#else
 #pragma unroll
       for (int k = 0; k < 3; ++k) st.L[k] = fmaf(st.T[k], PT_SKY, st.L[k]);
+#endif
       alive = false;
     }
   }
@@ -448,7 +548,11 @@ __device__ __forceinline__ bool path_step_pair(const Scene& S, int32_t* stack, P
 }
 
 __device__ __forceinline__ void store_path_pixel(const Scene& S, const PathState& st) {
+#ifdef PT_LIGHTS
+  store_out(S, st.out, st.alpha | lights_rgb(S, st));
+#else
   store_out(S, st.out, st.alpha | (to8(st.L[0]) << 16) | (to8(st.L[1]) << 8) | to8(st.L[2]));
+#endif
 }
 // st.xy / st.out from st.task (the queued forms: a path's pixel once, not per vertex)
 __device__ __forceinline__ void path_pixel(const Scene& S, PathState& st) {
@@ -606,17 +710,29 @@ __device__ __forceinline__ void accum_restart(const Scene& S, PathState& st, uin
     st.d[k] = r.d[k];
     st.L[k] = 0.0f;
   }
+#ifdef PT_LIGHTS
+  lights_zero(S, st);
+#endif
 }
-__device__ __forceinline__ void accum_add(uint4& rec, const PathState& st) {
+// (under PT_LIGHTS a sample is the several-light frame's 8-bit value, the rounded mean)
+__device__ __forceinline__ void accum_add(const Scene& S, uint4& rec, const PathState& st) {
+#ifdef PT_LIGHTS
+  const uint32_t c = lights_rgb(S, st);
+  rec.x += (c >> 16) & 0xffu;
+  rec.y += (c >> 8) & 0xffu;
+  rec.z += c & 0xffu;
+#else
+  (void)S;
   rec.x += to8(st.L[0]);
   rec.y += to8(st.L[1]);
   rec.z += to8(st.L[2]);
+#endif
 }
 // lane_path's tail: the launch's samples of this lane's pixel, in the wave's
 // vertex-loop form (lane_path's comments)
 __device__ __forceinline__ void accum_path(const Scene& S, int32_t* stack, Counters& cnt, uint32_t xy,
                                            uint32_t out, uint32_t color, int32_t hit, float th, bool in,
-                                           bool path, bool pair, bool coop) {
+                                           bool path, bool pair, bool coop, float* lacc) {
   const uint32_t ns = ((S.lw3 & RT_LW_ACCUM_K_MASK) >> RT_LW_ACCUM_K_SHIFT) + 1u;
   const uint32_t abuf = accum_buf(S);
   if (in && !path) {  // no path starts here: every sample is the primary colour
@@ -634,6 +750,11 @@ __device__ __forceinline__ void accum_path(const Scene& S, int32_t* stack, Count
   st.xy = xy;
   st.out = out;
   st.alpha = color & 0xff000000u;
+#ifdef PT_LIGHTS
+  st.lacc = lacc;
+#else
+  (void)lacc;
+#endif
   if (pair) {
     // every lane stays in the loop until the wave's last sample ends (helpers
     // trace their owner's shadow ray)
@@ -643,7 +764,7 @@ __device__ __forceinline__ void accum_path(const Scene& S, int32_t* stack, Count
       accum_restart(S, st, color, hit, th, S.seed + rec.w + j);
       bool act = path;
       for (uint32_t v = 0; __ballot(act) != 0; ++v) act = path_step_pair(S, stack, st, v, act, cnt);
-      if (path) accum_add(rec, st);
+      if (path) accum_add(S, rec, st);
     }
     if (path) {
       rec.w += ns;
@@ -672,7 +793,7 @@ __device__ __forceinline__ void accum_path(const Scene& S, int32_t* stack, Count
       accum_restart(S, st, color, hit, th, S.seed + rec.w + j);
       bool act = true;
       for (uint32_t v = 0; act; ++v) act = path_step<1>(S, pstack, st, v, act, cnt, hi ? 1u : 0u);
-      accum_add(rec, st);
+      accum_add(S, rec, st);
     }
     if (own) {
       rec.w += ns;
@@ -685,7 +806,7 @@ __device__ __forceinline__ void accum_path(const Scene& S, int32_t* stack, Count
     accum_restart(S, st, color, hit, th, S.seed + rec.w + j);
     for (uint32_t v = 0; path_step<0>(S, stack, st, v, true, cnt); ++v) {
     }
-    accum_add(rec, st);
+    accum_add(S, rec, st);
   }
   rec.w += ns;
   accum_store(S, abuf, out, rec, st.alpha);
@@ -693,8 +814,9 @@ __device__ __forceinline__ void accum_path(const Scene& S, int32_t* stack, Count
 #endif  // PT_ACCUM
 
 // one pixel's whole path on its own lane (no compaction)
+// (lacc: under PT_LIGHTS the lane's column of the per-light accumulators)
 __device__ __forceinline__ void lane_path(const vx_task_t& task, const Scene& S, int32_t* stack,
-                                          Counters& cnt) {
+                                          Counters& cnt, float* lacc = nullptr) {
   const uint32_t t = task.blockIdx.x;
   // the chunk's task map in scalar registers (every lane runs the same chunk)
   const ChunkMap cm = chunk_map(S, task_args(S), (uint32_t)__builtin_amdgcn_readfirstlane(t) >> 6);
@@ -708,8 +830,14 @@ __device__ __forceinline__ void lane_path(const vx_task_t& task, const Scene& S,
   // without the lists, paired vertices (path_step_pair: a list scan and a BVH
   // walk cannot share one loop)
   const bool split = __ballot(1) == ~0ull && (__ballot(in) >> 32) == 0;
+#ifdef PT_LIGHTS
+  // (every light of the table has lists; the argument block's slist_on is the single light's)
+  const bool pair = false;
+  const bool coop = split && (RT_ONLY_BVH4H || (S.flags & RT_FLAG_BVH4H));
+#else
   const bool pair = PT_PAIR && !S.slist_on && split;
   const bool coop = S.slist_on && split && (RT_ONLY_BVH4H || (S.flags & RT_FLAG_BVH4H));
+#endif
   cnt.primary += in;
   const bool tie_high = (S.flags & RT_FLAG_TIE_HIGH) != 0;
   // primary visibility: the raster's winner at this pixel (trace_primary)
@@ -722,7 +850,7 @@ __device__ __forceinline__ void lane_path(const vx_task_t& task, const Scene& S,
   const float th = hit >= 0 ? plane_t(S, r, hit) : 0.0f;
   const bool path = hit >= 0 && secondary_ok(th);  // a path starts at the winner's plane
 #ifdef PT_ACCUM
-  accum_path(S, stack, cnt, x | (y << 16), out, color, hit, th, in, path, pair, coop);
+  accum_path(S, stack, cnt, x | (y << 16), out, color, hit, th, in, path, pair, coop, lacc);
 #else
   if (!path && in) store_out(S, out, color);
   if (!path && !pair && !coop) return;
@@ -743,6 +871,12 @@ __device__ __forceinline__ void lane_path(const vx_task_t& task, const Scene& S,
     st.d[k] = r.d[k];
     st.L[k] = 0.0f;
   }
+#ifdef PT_LIGHTS
+  st.lacc = lacc;  // (in the lane-pair form both lanes of a pair keep the path's accumulators)
+  lights_zero(S, st);
+#else
+  (void)lacc;
+#endif
   if (pair) {
     // every lane stays in the loop (helpers trace their owner's shadow ray)
     bool act = path;
@@ -856,9 +990,16 @@ VX_MAIN(rt_kernel_arg_t, arg, PT_BLOCK) {
   }
 #else
   int32_t* stack = &s_pt.stack[threadIdx.x >> 6][0][lane_id()];
+#ifdef PT_LIGHTS
+  float* lacc = &s_pt.lacc[threadIdx.x >> 6][0][lane_id()];
+  const int rc = vx_spawn_tasks(
+      S.num_tasks,
+      [&](const vx_task_t& task, const Scene* s) { lane_path(task, *s, stack, cnt, lacc); }, &S);
+#else
   const int rc = vx_spawn_tasks(
       S.num_tasks,
       [&](const vx_task_t& task, const Scene* s) { lane_path(task, *s, stack, cnt); }, &S);
+#endif
 #endif
 #ifndef RT_STAMPS  // the stamp image keeps slots 4-6 for its cycle accumulators
   flush(RT_STAT_PRIMARY, cnt.primary);

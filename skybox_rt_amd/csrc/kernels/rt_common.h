@@ -304,6 +304,27 @@ static inline uint32_t rt_lights_mix(uint32_t argb, uint32_t occluded, uint32_t 
   }
   return out;
 }
+// A path-traced frame lit by several point lights (pt_kernel.hip PT_LIGHTS, images pt_lights /
+// pt_lights_accum; vx_rt.h rt_renderer_set_path_lights) reads the first count <=
+// RT_MAX_PATH_LIGHTS entries of the same table, every one with lists (slist_on 1).  The cap is
+// the kernel's LDS: three float accumulators per light and lane, 768 B a light in a one-wave
+// workgroup, next to the 6 912 B traversal stack -- 8 lights keep 12 workgroups on a CU.
+#define RT_MAX_PATH_LIGHTS 8u
+// One channel of such a frame's pixel: the rounded mean (2 * sum + k) / (2 * k) in integer
+// division of the k single-light 8-bit values (sum = their sum, 1 <= k <= RT_MAX_PATH_LIGHTS),
+// the accumulation resolve on {sum, k}.  As in rt_lights_mix the division is a multiplication
+// by m = ceil(2^20 / d), d = 2k <= 16: with e = m * d - 2^20 in [0, d), n * m / 2^20 = n / d +
+// n * e / (d * 2^20), whose second term stays below 1 / d -- so the floor is floor(n / d) --
+// while n * e < 2^20; n = 2 * sum + k <= 2 * 8 * 255 + 8 = 4088 and e <= 15 give n * e <=
+// 61 320.  n * m < 2^12 * 2^19 fits 32 bits.  The kernel and the host (rt_path_lights_resolve)
+// share this text.
+#if defined(__HIPCC__)
+__host__ __device__
+#endif
+static inline uint32_t rt_path_lights_mean(uint32_t sum, uint32_t k) {
+  const uint32_t d = 2u * k, m = (0x100000u + d - 1u) / d;
+  return ((2u * sum + k) * m) >> 20;
+}
 // padding entries after the last tail list (the first tail pid): the fold
 // loads the entry two ahead and the record one ahead of the one it tests
 #define RT_OLIST_PAD 2u

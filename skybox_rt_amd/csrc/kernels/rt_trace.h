@@ -63,7 +63,9 @@
 //                  rt_lights_arg_t), every queued shadow ray tested against
 //                  each of them in one drain (rt_kernel.hip shadow_drain);
 //                  shadow_ray and occluded_list then take the light and its
-//                  list bases as parameters
+//                  list bases as parameters (occluded_list_coop too: the path
+//                  tracer's images pt_lights / pt_lights_accum, pt_kernel.hip
+//                  PT_LIGHTS, read the same table at every path vertex)
 #ifndef RT_LIGHTS
 #define RT_LIGHTS 0
 #endif
@@ -1160,6 +1162,18 @@ __device__ __forceinline__ int32_t trace_coop(const Scene& S, const Ray& r, int3
 // testing the first two, the upper the other two; the verdict is whether any
 // record occludes (order-free), the tests counted are the sequential scan's
 // (the upper lane's only when the lower lane's two did not occlude)
+#if RT_LIGHTS
+// (the lists of one light of the table, as occluded_list takes them)
+__device__ __forceinline__ bool occluded_list_coop(const Scene& S, const Ray& s, bool act, int32_t skip,
+                                                   bool hi, Counters& cnt, uint32_t sidx, uint32_t slist,
+                                                   uint32_t slist_n) {
+  if (!act) return false;
+  const uint32_t cell = slist_cell(s, slist_n);
+  const uint32_t off = S.A.ld_u32(sidx + 8u * cell), n = S.A.ld_u32(sidx + 8u * cell + 4u);
+  const uint32_t e0 = hi ? 2u : 0u;
+  const float lim = slist_limit(s);
+  uint32_t o = slist + 48u * (off + e0);
+#else
 __device__ __forceinline__ bool occluded_list_coop(const Scene& S, const Ray& s, bool act, int32_t skip,
                                                    bool hi, Counters& cnt) {
   if (!act) return false;
@@ -1168,6 +1182,7 @@ __device__ __forceinline__ bool occluded_list_coop(const Scene& S, const Ray& s,
   const uint32_t e0 = hi ? 2u : 0u;
   const float lim = slist_limit(s);
   uint32_t o = S.slist + 48u * (off + e0);
+#endif
   for (uint32_t q = 0; q < n; q += 4, o += 192u) {
     bool hit = false, end = false;  // end: a record past the bound (occluded_list)
     RT_CNT(uint32_t tests = 0;)

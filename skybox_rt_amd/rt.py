@@ -81,6 +81,7 @@ class LightInfo(C.Structure):
 
 
 RT_MAX_LIGHTS = 16
+RT_MAX_PATH_LIGHTS = 8
 
 
 class RenderParams(C.Structure):
@@ -165,6 +166,7 @@ def lib():
             "rt_renderer_accum_samples": [vp, C.POINTER(u32)],
             "rt_read_accum": [vp, vp, u64],
             "rt_renderer_set_lights": [vp, vp, u32],
+            "rt_renderer_set_path_lights": [vp, vp, u32],
             "rt_renderer_lights_info": [vp, C.POINTER(LightInfo), u32, C.POINTER(u32)],
             "rt_renderer_export_light_lists": [vp, u32, u32, vp, u64, C.POINTER(u64)],
         }
@@ -176,6 +178,8 @@ def lib():
         h.rt_accum_resolve.restype = u32
         h.rt_lights_resolve.argtypes = [u32, u32, u32]
         h.rt_lights_resolve.restype = u32
+        h.rt_path_lights_resolve.argtypes = [C.POINTER(u32), u32, u32]
+        h.rt_path_lights_resolve.restype = u32
         h.rt_last_error.restype = C.c_char_p
         h.rt_last_error.argtypes = []
         _h = h
@@ -369,6 +373,20 @@ class Renderer:
         waits for the device.  set_light() and configure() return to one light."""
         arr = np.ascontiguousarray(np.asarray(lights, np.float32).reshape(-1, 3))
         _check(lib().rt_renderer_set_lights(self._h, arr.ctypes.data, arr.shape[0]), "rt_renderer_set_lights")
+        self.params.light[:] = [float(x) for x in arr[0]]
+
+    # several lights on a path frame (vx_rt.h rt_renderer_set_path_lights; images pt_lights / pt_lights_accum)
+    def set_path_lights(self, lights) -> None:
+        """Light the configured path-traced frame by 1..8 point lights (clip x,
+        y, w each): render() / start() frames and accumulate() samples after it
+        are, per pixel and channel, the rounded mean of the single-light path
+        frames of the same seed, traced in one launch -- every bounce ray once,
+        one shadow ray per light at each vertex.  Builds a set of shadow lists
+        per light and waits for the device; starts accumulated records over.
+        set_light() and configure() return to one light."""
+        arr = np.ascontiguousarray(np.asarray(lights, np.float32).reshape(-1, 3))
+        _check(lib().rt_renderer_set_path_lights(self._h, arr.ctypes.data, arr.shape[0]),
+               "rt_renderer_set_path_lights")
         self.params.light[:] = [float(x) for x in arr[0]]
 
     def lights_info(self) -> list:
@@ -647,6 +665,14 @@ def lights_resolve(argb: int, occluded: int, k: int) -> int:
     `occluded` of its k lights do not see -- per channel (2 * sum + k) // (2 * k),
     sum = (k - occluded) * c + occluded * (c >> 1); argb's alpha."""
     return int(lib().rt_lights_resolve(int(argb) & 0xFFFFFFFF, int(occluded), int(k)))
+
+
+def path_lights_resolve(sums, k: int, alpha_argb: int) -> int:
+    """rt_path_lights_resolve: the pixel whose k single-light 8-bit values sum
+    to sums = (R, G, B) -- per channel (2 * sum + k) // (2 * k) -- under
+    alpha_argb's alpha byte."""
+    arr = (C.c_uint32 * 3)(*[int(x) for x in sums])
+    return int(lib().rt_path_lights_resolve(arr, int(k), int(alpha_argb) & 0xFFFFFFFF))
 
 
 def deinterleave_tiles(shards, width: int, height: int) -> np.ndarray:
