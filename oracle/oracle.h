@@ -217,6 +217,16 @@ void orc_tex_lod(uint32_t logw, uint32_t logh, uint32_t dst_w, uint32_t dst_h, u
 void orc_tex_render(const uint8_t* tex, const uint32_t* mipoff, uint32_t logw, uint32_t logh,
                     uint32_t format, uint32_t wrap, uint32_t filter, uint32_t dst_w, uint32_t dst_h,
                     uint32_t num_tasks, uint32_t* dst);
+/* the same pixels from explicit coordinate tables (u per column, v per row,
+ * TFixed<23>) at a given lod / frac */
+void orc_tex_render_tab(const uint8_t* tex, const uint32_t* mipoff, uint32_t logw, uint32_t logh,
+                        uint32_t format, uint32_t wrap, uint32_t filter, uint32_t lod, uint32_t frac,
+                        uint32_t dst_w, uint32_t dst_h, const int32_t* utab, const int32_t* vtab,
+                        uint32_t* dst);
+/* orc_tex_read (gfx.h) over n coordinate pairs with the whole sampler state given */
+void orc_tex_read_n(const uint8_t* tex, uint32_t logw, uint32_t logh, uint32_t format,
+                    uint32_t filter, uint32_t wrapu, uint32_t wrapv, uint32_t n, const int32_t* u,
+                    const int32_t* v, uint32_t* out);
 
 #ifdef __cplusplus
 }

@@ -379,6 +379,37 @@ def tex_render(argb: np.ndarray, fmt: int = 0, wrap: int = 0, filt: int = 0, sca
     return dst
 
 
+def tex_read(tex_bytes, logw, logh, fmt, filt, wrapu, wrapv, u, v) -> np.ndarray:
+    """orc_tex_read (gfx.c: the sampler at lod 0) with the whole state given,
+    over coordinate arrays u, v (int32 TFixed<23>) -> uint32[] ARGB8888."""
+    L = lib()
+    L.orc_tex_read_n.argtypes = [C.c_void_p] + [C.c_uint32] * 7 + [C.c_void_p] * 3
+    L.orc_tex_read_n.restype = None
+    tex = np.ascontiguousarray(tex_bytes, np.uint8)
+    u = np.ascontiguousarray(u, np.int32)
+    v = np.ascontiguousarray(v, np.int32)
+    out = np.zeros(u.size, np.uint32)
+    L.orc_tex_read_n(tex.ctypes.data, logw, logh, fmt, filt, wrapu, wrapv, u.size, u.ctypes.data,
+                     v.ctypes.data, out.ctypes.data)
+    return out
+
+
+def tex_render_tab(texels, mipoff, logw, logh, fmt, wrap, filt, lod, frac, utab, vtab) -> np.ndarray:
+    """orc_tex_render_tab: the tex app's pixels from explicit coordinate
+    tables (u per column, v per row) at a given lod / frac -> uint32[h, w]."""
+    L = lib()
+    L.orc_tex_render_tab.argtypes = [C.c_void_p, C.c_void_p] + [C.c_uint32] * 9 + [C.c_void_p] * 3
+    L.orc_tex_render_tab.restype = None
+    tex = np.ascontiguousarray(texels, np.uint8)
+    mip = np.ascontiguousarray(mipoff, np.uint32)
+    ut = np.ascontiguousarray(utab, np.int32)
+    vt = np.ascontiguousarray(vtab, np.int32)
+    dst = np.zeros((vt.size, ut.size), np.uint32)
+    L.orc_tex_render_tab(tex.ctypes.data, mip.ctypes.data, logw, logh, fmt, wrap, filt, lod, frac,
+                         ut.size, vt.size, ut.ctypes.data, vt.ctypes.data, dst.ctypes.data)
+    return dst
+
+
 # ---- linear BVH (oracle/lbvh.c) -------------------------------------------
 def lbvh_build(verts: np.ndarray, geom: np.ndarray):
     """verts float32[n, 3, 3] clip (x, y, w) corners, geom float32[n, 12] their

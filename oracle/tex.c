@@ -9,10 +9,18 @@
  * palette64}_ref_g0..g2 = point / bilinear / trilinear), which fix the
  * un-vendored cocogfx LoadImage format conversion inferred here: truncation
  * to the channel width, luminance = the red channel, 1-bit alpha = (a != 0).
- * Unpinned: texels of mip levels >= 1 (cocogfx GenerateMipmaps is not
- * vendored and no golden samples them -- at scale 1 the trilinear blend
- * factor is 0); restated as a 2x2 box filter of the decoded level above,
- * truncating, re-encoded with the same conversion. */
+ * The goldens are all CLAMP at scale 1 with coordinates inside (0, 1); the
+ * rest of the sampler's state space (wrap modes out of range, lods, the
+ * trilinear blend, the int32 extremes) is pinned to an independent model,
+ * tests/tex_reference.py with the hand-worked tests/tex_known_answers.py:
+ * orc_tex_read, orc_tex_render, orc_tex_render_tab, orc_tex_lod and
+ * orc_tex_build equal it over the sweeps of tests/tex_sweep.py
+ * (tests/test_tex_unit_cpu.py).
+ * Unpinned by any reference artefact: texels of mip levels >= 1 (cocogfx
+ * GenerateMipmaps is not vendored and no golden samples them -- at scale 1
+ * the trilinear blend factor is 0); restated as a 2x2 box filter of the
+ * decoded level above, truncating, re-encoded with the same conversion.  The
+ * model and the product host build the same chain: agreement, not a pin. */
 #include <math.h>
 #include <stdlib.h>
 #include <string.h>
@@ -152,6 +160,51 @@ static uint32_t lerp8888_(uint32_t a, uint32_t b, uint32_t f) {  /* graphics.h:8
   return ((p + q) >> 8) & 0x00ff00ffu;
 }
 
+/* kernel.cpp:83-100 for one pixel: the sample at `lod`, for filter 2 blended
+ * with the one at the next lod by `frac` */
+static uint32_t pixel(const uint8_t* tex, const uint32_t* mipoff, uint32_t logw, uint32_t logh,
+                      uint32_t format, uint32_t wrap, uint32_t filter, uint32_t lod, uint32_t frac,
+                      int32_t xu, int32_t xv) {
+  if (filter != 2) return sample(tex, mipoff, logw, logh, format, filter, wrap, lod, xu, xv);
+  const uint32_t lodn = lod + 1 < VX_TEX_LOD_MAX ? lod + 1 : VX_TEX_LOD_MAX;
+  const uint32_t t0 = sample(tex, mipoff, logw, logh, format, 1, wrap, lod, xu, xv);
+  const uint32_t t1 = sample(tex, mipoff, logw, logh, format, 1, wrap, lodn, xu, xv);
+  const uint32_t cl = lerp8888_(t0 & 0x00ff00ffu, t1 & 0x00ff00ffu, frac);
+  const uint32_t ch = lerp8888_((t0 >> 8) & 0x00ff00ffu, (t1 >> 8) & 0x00ff00ffu, frac);
+  return (ch << 8) | cl;
+}
+
+/* The same pixels from explicit tables (the product kernel's argument:
+ * TFixed<23> u per column, v per row, lod and frac given), so that
+ * coordinates outside [0, 1) and any lod / frac can be driven
+ * (tests/tex_sweep.py's image sweep). */
+void orc_tex_render_tab(const uint8_t* tex, const uint32_t* mipoff, uint32_t logw, uint32_t logh,
+                        uint32_t format, uint32_t wrap, uint32_t filter, uint32_t lod, uint32_t frac,
+                        uint32_t dst_w, uint32_t dst_h, const int32_t* utab, const int32_t* vtab,
+                        uint32_t* dst) {
+  for (uint32_t y = 0; y < dst_h; ++y)
+    for (uint32_t x = 0; x < dst_w; ++x)
+      dst[(size_t)y * dst_w + x] =
+          pixel(tex, mipoff, logw, logh, format, wrap, filter, lod, frac, utab[x], vtab[y]);
+}
+
+/* orc_tex_read over a table of coordinates, with the whole sampler state
+ * given (wrapu and wrapv apart): tests/test_tex_unit_cpu.py */
+void orc_tex_read_n(const uint8_t* tex, uint32_t logw, uint32_t logh, uint32_t format,
+                    uint32_t filter, uint32_t wrapu, uint32_t wrapv, uint32_t n, const int32_t* u,
+                    const int32_t* v, uint32_t* out) {
+  orc_dcstate_t s;
+  memset(&s, 0, sizeof(s));
+  s.tex_base = tex;
+  s.tex_logw = logw;
+  s.tex_logh = logh;
+  s.tex_format = format;
+  s.tex_filter = filter ? VX_TEX_FILTER_BILINEAR : VX_TEX_FILTER_POINT;
+  s.tex_wrapu = wrapu;
+  s.tex_wrapv = wrapv;
+  for (uint32_t i = 0; i < n; ++i) out[i] = orc_tex_read(&s, u[i], v[i]);
+}
+
 /* tex/kernel.cpp kernel_body over all num_tasks tasks: dst (dst_w x dst_h
  * ARGB8888, row 0 = top) from the texture.  filter: 0 point, 1 bilinear,
  * 2 bilinear + blend with the next lod (tex/main.cpp -g). */
@@ -162,7 +215,6 @@ void orc_tex_render(const uint8_t* tex, const uint32_t* mipoff, uint32_t logw, u
   const float dX = 1.0f / (float)dst_w, dY = 1.0f / (float)dst_h;
   uint32_t lod, frac;
   orc_tex_lod(logw, logh, dst_w, dst_h, &lod, &frac);
-  const uint32_t lodn = lod + 1 < VX_TEX_LOD_MAX ? lod + 1 : VX_TEX_LOD_MAX;
   for (uint32_t task = 0; task < num_tasks; ++task) {
     const uint32_t y0 = task * tile_h;
     const uint32_t y1 = y0 + tile_h < dst_h ? y0 + tile_h : dst_h;
@@ -172,16 +224,7 @@ void orc_tex_render(const uint8_t* tex, const uint32_t* mipoff, uint32_t logw, u
       for (uint32_t x = 0; x < dst_w; ++x) {
         const int32_t xu = fx_from_float_dev(fu, VX_TEX_FXD_FRAC);
         const int32_t xv = fx_from_float_dev(fv, VX_TEX_FXD_FRAC);
-        uint32_t color;
-        if (filter == 2) {
-          const uint32_t t0 = sample(tex, mipoff, logw, logh, format, 1, wrap, lod, xu, xv);
-          const uint32_t t1 = sample(tex, mipoff, logw, logh, format, 1, wrap, lodn, xu, xv);
-          const uint32_t cl = lerp8888_(t0 & 0x00ff00ffu, t1 & 0x00ff00ffu, frac);
-          const uint32_t ch = lerp8888_((t0 >> 8) & 0x00ff00ffu, (t1 >> 8) & 0x00ff00ffu, frac);
-          color = (ch << 8) | cl;
-        } else {
-          color = sample(tex, mipoff, logw, logh, format, filter, wrap, lod, xu, xv);
-        }
+        const uint32_t color = pixel(tex, mipoff, logw, logh, format, wrap, filter, lod, frac, xu, xv);
         dst[(size_t)y * dst_w + x] = color;
         fu += dX;
       }

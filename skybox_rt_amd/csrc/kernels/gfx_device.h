@@ -6,7 +6,11 @@
 // (draw3d/gpu_sw.h); the arithmetic lives in sim/common/graphics.cpp and the
 // draw3d shader macros (draw3d/kernel.cpp:16-79).  Restated here as inline
 // device functions with bit-identical integer/float behaviour (pinned through
-// the oracle, which matches the reference's golden images exactly).  Records
+// the oracle, which matches the reference's golden images exactly; the
+// sampler -- tex_read, every tex_read_fmt<FMT> and tex_read_any -- also
+// directly to the independent model tests/tex_reference.py, over every format
+// x filter x (wrapu, wrapv) pair and out-of-range coordinates, through the
+// tex_kat image: tests/test_gpu_tex_unit.py).  Records
 // are fetched from the arena with buffer loads (vx_arena) into registers.
 #pragma once
 
