@@ -31,7 +31,7 @@ int run(rt_renderer* r, vx_buffer_h argb, const rt_setup_arg_t& a, uint32_t* lau
   static const bool trace = std::getenv("RT_SETUP_TRACE") != nullptr;  // per-launch phases to stderr
   const auto t0 = std::chrono::steady_clock::now();
   if (vx_copy_to_dev(argb, &a, 0, sizeof(a)) != 0) return set_error("vx_copy_to_dev failed");
-  if (vx_start(r->dev, r->setup_krnl, argb) != 0) return set_error("vx_start failed");
+  if (vx_start(r->dev, r->img[rtimg::IMG_SETUP], argb) != 0) return set_error("vx_start failed");
   if (vx_ready_wait(r->dev, VX_MAX_TIMEOUT) != 0) return set_error("vx_ready_wait failed");
   ++*launches;
   if (trace)
@@ -66,7 +66,7 @@ void add_fill(rt_setup_arg_t* g, uint64_t addr, uint64_t words, uint32_t value) 
 
 int device_ingest(rt_renderer* r, bool records) {
   const rt_scene* s = r->sc;
-  if (load_image(r, "rt_setup.vxbin", &r->setup_krnl)) return -1;
+  if (load_images(r, rtimg::GRP_SETUP)) return -1;
   const size_t np = s->scene.prims.size();
   std::vector<float> verts(np * 32, 0.0f);
   std::vector<uint32_t> pdc(np, 0);
@@ -193,7 +193,7 @@ int run_seq(rt_renderer* r, rt_setup_arg_t& g, const Seq& q, uint32_t* launches)
   // (the driver refuses groups longer than its slots allow: then one run each)
   const bool grouped = r->launch_group && r->launch_group(r->dev, x.n | VX_HIP_GROUP_UNTIMED) == 0;
   for (uint32_t i = 0; i < x.n; ++i)
-    if (r->set_tag(r->dev, i) != 0 || vx_start(r->dev, r->setup_krnl, r->su.args.h) != 0) {
+    if (r->set_tag(r->dev, i) != 0 || vx_start(r->dev, r->img[rtimg::IMG_SETUP], r->su.args.h) != 0) {
       if (grouped) r->launch_group(r->dev, 0);  // abandon the half-issued group
       return set_error("vx_start failed");
     }

@@ -45,14 +45,33 @@ int fail(const std::string& m, int code = -1) {
   return code;
 }
 
-std::string lib_dir() {
+std::string find_lib_dir() {
   Dl_info info;
-  if (dladdr((void*)&lib_dir, &info) && info.dli_fname) {
+  if (dladdr((void*)&find_lib_dir, &info) && info.dli_fname) {
     std::string p(info.dli_fname);
     auto pos = p.rfind('/');
     if (pos != std::string::npos) return p.substr(0, pos);
   }
   return ".";
+}
+
+// (looked up once: every image group asks, and dladdr walks the process's loaded objects)
+const std::string& lib_dir() {
+  static const std::string dir = find_lib_dir();
+  return dir;
+}
+
+bool file_exists(const std::string& path) {
+  FILE* f = std::fopen(path.c_str(), "rb");
+  if (f) std::fclose(f);
+  return f != nullptr;
+}
+
+// the one upload of a kernel image file
+int upload_image(rt_renderer* r, const std::string& path, vx_buffer_h* out) {
+  if (vx_upload_kernel_file(r->dev, path.c_str(), out) == 0) return 0;
+  *out = nullptr;
+  return fail("cannot upload kernel " + path);
 }
 
 double ms_since(std::chrono::steady_clock::time_point t0) {
@@ -67,7 +86,6 @@ std::string library_dir() { return lib_dir(); }
 }  // namespace rtapp
 
 using rtapp::DevBuf;
-using rtapp::load_image;
 using rtapp::upload;
 
 extern "C" {
@@ -318,24 +336,11 @@ int rt_renderer_create(rt_scene_h s, const char* kernel_dir, rt_renderer_h* out)
   if (std::max(bvh.depth, bvh.stack4) > RT_STACK_DEEP)
     return fail("BVH too deep for the traversal stack");
   r->deep = deep;
-  const char* names[4][2] = {
-      {deep ? "rt_kernel_deep.vxbin" : "rt_kernel.vxbin",
-       deep ? "rt_kernel_deep_stats.vxbin" : "rt_kernel_stats.vxbin"},
-      {deep ? "pt_kernel_deep.vxbin" : "pt_kernel.vxbin",
-       deep ? "pt_kernel_deep_stats.vxbin" : "pt_kernel_stats.vxbin"},
-      {"rt_flat.vxbin", "rt_flat_stats.vxbin"},
-      {"raster_kernel.vxbin", nullptr}};
   // images missing from kernel_dir (e.g. an A/B variant directory holding
   // only rt_kernel*) come from the library directory
-  for (int m = 0; m < 4; ++m)
-    for (int i = 0; i < 2; ++i) {
-      if (!names[m][i]) continue;
-      std::string path = dir + "/" + names[m][i];
-      if (FILE* f = std::fopen(path.c_str(), "rb")) std::fclose(f);
-      else path = lib_dir() + "/" + names[m][i];
-      if (vx_upload_kernel_file(r->dev, path.c_str(), &r->krnl[m][i]) != 0)
-        return fail("cannot upload kernel " + path);
-    }
+  if (rtapp::load_images(r.get(), deep ? rtimg::GRP_DEEP : rtimg::GRP_REGULAR) != 0 ||
+      rtapp::load_images(r.get(), rtimg::GRP_MODES) != 0)
+    return -1;
   r->mem_ptr = (vx_hip_mem_ptr_t)vx_driver_symbol("vx_hip_mem_ptr");
   r->stream = (vx_hip_stream_t)vx_driver_symbol("vx_hip_stream");
   r->last_run = (vx_hip_last_run_t)vx_driver_symbol("vx_hip_last_run");
@@ -360,31 +365,12 @@ int rt_renderer_create(rt_scene_h s, const char* kernel_dir, rt_renderer_h* out)
   // the two-kernel path tracer's images (binary16 BVH4 only; the others run
   // the one-kernel pt_kernel images), from the kernel directory itself: a
   // directory without them (e.g. lib/pt_compact) runs its own pt_kernel
-  if (!deep) {
-    const char* pq_names[2][2] = {{"pt_primary.vxbin", "pt_primary_stats.vxbin"},
-                                  {"pt_queue.vxbin", "pt_queue_stats.vxbin"}};
-    bool all = true;
-    for (int m = 0; m < 2; ++m)
-      for (int i = 0; i < 2; ++i)
-        if (FILE* f = std::fopen((dir + "/" + pq_names[m][i]).c_str(), "rb")) std::fclose(f);
-        else all = false;
-    for (int m = 0; m < 2 && all; ++m)
-      for (int i = 0; i < 2; ++i)
-        if (vx_upload_kernel_file(r->dev, (dir + "/" + pq_names[m][i]).c_str(), &r->krnl_pq[m][i]) != 0)
-          return fail("cannot upload kernel " + dir + "/" + pq_names[m][i]);
-    // the BVH-walk primary+shadow images (RT_RENDER_BVH_WALK), from the
-    // kernel directory or the library's
-    const char* bvh_names[2] = {"rt_bvh.vxbin", "rt_bvh_stats.vxbin"};
-    for (int i = 0; i < 2; ++i) {
-      std::string path = dir + "/" + bvh_names[i];
-      if (FILE* f = std::fopen(path.c_str(), "rb")) std::fclose(f);
-      else path = lib_dir() + "/" + bvh_names[i];
-      if (vx_upload_kernel_file(r->dev, path.c_str(), &r->krnl_bvh[i]) != 0)
-        return fail("cannot upload kernel " + path);
-    }
-  }
+  // (then the BVH-walk primary+shadow images, RT_RENDER_BVH_WALK, from the kernel directory or
+  // the library's)
+  if (!deep && (rtapp::load_images(r.get(), rtimg::GRP_PQ) != 0 || rtapp::load_images(r.get(), rtimg::GRP_BVH) != 0))
+    return -1;
   // a scene with an ordered tail renders its plain and shadow frames with rt_om
-  if (!s->tail_prims.empty() && load_image(r.get(), "rt_om.vxbin", &r->krnl_om) != 0) return -1;
+  if (!s->tail_prims.empty() && rtapp::load_images(r.get(), rtimg::GRP_OM) != 0) return -1;
   rt_kernel_arg_t& a = r->arg;
   std::memset(&a, 0, sizeof(a));
   // 3 padding records: the kernel fetches all 4 slots of a leaf at once
@@ -505,7 +491,8 @@ static uint32_t lane_grid_of(rt_renderer* r) {
   r->lane_grid = 0;
   uint64_t ia = 0;
   uint32_t block = 0, mgrid = 0;
-  if (r->lane_chunks > 1 && r->krnl[0][0] && vx_mem_address(r->krnl[0][0], &ia) == 0 &&
+  const vx_buffer_h rt = r->img[rtimg::mode_image(0, 0, r->deep)];
+  if (r->lane_chunks > 1 && rt && vx_mem_address(rt, &ia) == 0 &&
       r->launch_shape(r->dev, ia, &block, &mgrid) == 0 && block >= 64) {
     const uint32_t chunks = (r->arg.num_tasks + 63u) / 64u, per = r->lane_chunks * (block / 64u);
     const uint32_t g = std::max(1u, (chunks + per - 1u) / per);
@@ -523,7 +510,8 @@ static uint32_t tier_groups_of(rt_renderer* r, int k, uint32_t grid, bool laned)
   if (!r->img_shape_known[k]) {
     r->img_shape_known[k] = true;
     uint64_t ia = 0;
-    if (!(r->launch_shape && r->krnl[0][k] && vx_mem_address(r->krnl[0][k], &ia) == 0 &&
+    const vx_buffer_h rt = r->img[rtimg::IMG_RT + k];  // (bg_ok: not deep)
+    if (!(r->launch_shape && rt && vx_mem_address(rt, &ia) == 0 &&
           r->launch_shape(r->dev, ia, &r->img_block[k], &r->img_grid[k]) == 0))
       r->img_block[k] = r->img_grid[k] = 0;
   }
@@ -571,41 +559,12 @@ int rt_renderer_set_light(rt_renderer_h r, const float light[3]) {
 
 // ---- several lights (vx_rt.h; NO REFERENCE) --------------------------------
 
-int rt_renderer_set_lights(rt_renderer_h r, const float (*lights)[3], uint32_t n) {
-  if (!r) return fail("null argument");
-  if (!r->configured) return fail("renderer not configured");
-  if (n < 1 || n > RT_MAX_LIGHTS) return fail("rt_renderer_set_lights: 1 to 16 lights", -2);
-  if (!lights) return fail("null argument");
-  const uint32_t f = r->params.flags;
-  if (!(f & RT_RENDER_SHADOWS) || (f & (RT_RENDER_PATH | RT_RENDER_FLAT | RT_RENDER_RASTER | RT_RENDER_BVH_WALK)))
-    return fail("rt_renderer_set_lights: a plain RT_RENDER_SHADOWS frame only (no RT_RENDER_PATH / FLAT / RASTER / "
-                "BVH_WALK)", -2);
-  if (!r->sc->tail_prims.empty())
-    return fail("rt_renderer_set_lights: a scene with an ordered tail renders with one light (rt_om has no "
-                "several-light image)", -2);
-  // (a scene without geometry queues no shadow ray and walks no tree: any image serves it)
-  if (r->arg.num_geom > 0 && (r->deep || !(r->arg.flags & RT_FLAG_BVH4H)))
-    return fail("rt_renderer_set_lights: rt_lights walks the binary16 BVH4 only; this tree runs the generic "
-                "(deep) images", -2);
-  if (!r->krnl_lights[0]) {
-    // next to the rt_kernel.vxbin in use: the kernel directory's when it holds one
-    std::string dir = r->kdir;
-    if (FILE* fk = std::fopen((dir + "/rt_kernel.vxbin").c_str(), "rb")) std::fclose(fk);
-    else dir = lib_dir();
-    const char* names[2] = {"rt_lights.vxbin", "rt_lights_stats.vxbin"};
-    for (int i = 0; i < 2; ++i)
-      if (FILE* fa = std::fopen((dir + "/" + names[i]).c_str(), "rb")) std::fclose(fa);
-      else return fail("rt_renderer_set_lights: no " + std::string(names[i]) + " next to " + dir + "/rt_kernel.vxbin", -2);
-    for (int i = 0; i < 2; ++i)
-      if (vx_upload_kernel_file(r->dev, (dir + "/" + names[i]).c_str(), &r->krnl_lights[i]) != 0) {
-        for (int j = 0; j <= i; ++j) {
-          if (r->krnl_lights[j]) vx_mem_free(r->krnl_lights[j]);
-          r->krnl_lights[j] = nullptr;
-        }
-        return fail("cannot upload kernel " + dir + "/" + names[i]);
-      }
-  }
-  uint32_t launches = 0;
+// rt_renderer_set_lights / rt_renderer_set_path_lights behind their admission checks (`who`):
+// the images of `group`, a list set per light (lists false: none is built, the shadow rays walk
+// the BVH) and the light table; need_lists: a set that was not built is a refusal
+static int set_several_lights(rt_renderer_h r, const float (*lights)[3], uint32_t n, rtimg::Group group,
+                              const char* who, bool lists, bool need_lists) {
+  if (const int e = rtapp::load_images(r, group, who)) return e;
   if (n == 1) {
     // one light: rt_renderer_set_light with its lists queued at once
     const uint32_t defer = r->sl_defer;
@@ -617,12 +576,16 @@ int rt_renderer_set_lights(rt_renderer_h r, const float (*lights)[3], uint32_t n
   }
   // a list set per light, each chain behind the frames in flight; then the table, in stream
   // order ahead of every frame started after it
-  if (rtapp::build_light_sets(r, lights, n, r->sl_mode, &launches) != 0) return -1;
+  uint32_t launches = 0;
+  if (rtapp::build_light_sets(r, lights, n, lists, &launches) != 0) return -1;
   rt_lights_arg_t la{};
   la.count = n;
   la.slist_n = r->arg.slist_n;
   for (uint32_t i = 0; i < n; ++i) {
     const LightSet& l = r->lsets[i];
+    if (need_lists && !l.built)
+      return fail(std::string(who) + ": the light-space lists of light " + std::to_string(i) +
+                  " do not fit (pt_lights has no BVH shadow walk)", -2);
     std::memcpy(la.l[i].light, l.light, sizeof(l.light));
     la.l[i].slist_on = l.built ? 1u : 0u;
     la.l[i].sidx_addr = l.sidx_addr;
@@ -636,6 +599,25 @@ int rt_renderer_set_lights(rt_renderer_h r, const float (*lights)[3], uint32_t n
   r->nlights = n;
   r->lane_break = true;
   return 0;
+}
+
+int rt_renderer_set_lights(rt_renderer_h r, const float (*lights)[3], uint32_t n) {
+  if (!r) return fail("null argument");
+  if (!r->configured) return fail("renderer not configured");
+  if (n < 1 || n > RT_MAX_LIGHTS) return fail("rt_renderer_set_lights: 1 to 16 lights", -2);
+  if (!lights) return fail("null argument");
+  const uint32_t f = r->params.flags;
+  if (!(f & RT_RENDER_SHADOWS) || (f & (RT_RENDER_PATH | RT_RENDER_FLAT | RT_RENDER_RASTER | RT_RENDER_BVH_WALK)))
+    return fail("rt_renderer_set_lights: a plain RT_RENDER_SHADOWS frame only (no RT_RENDER_PATH / FLAT / RASTER / "
+                "BVH_WALK)", -2);
+  if (!r->sc->tail_prims.empty())
+    return fail("rt_renderer_set_lights: a scene with an ordered tail renders with one light (rt_om has no "
+                "several-light image)", -2);
+  // (a scene without geometry queues no shadow ray and walks no tree: any image serves it)
+  if (r->arg.num_geom > 0 && r->generic_tree())
+    return fail("rt_renderer_set_lights: rt_lights walks the binary16 BVH4 only; this tree runs the generic "
+                "(deep) images", -2);
+  return set_several_lights(r, lights, n, rtimg::GRP_LIGHTS, "rt_renderer_set_lights", r->sl_mode, false);
 }
 
 int rt_renderer_lights_info(rt_renderer_h r, rt_light_info_t* out, uint32_t max, uint32_t* n) {
@@ -710,65 +692,11 @@ int rt_renderer_set_path_lights(rt_renderer_h r, const float (*lights)[3], uint3
   if (!r->sl_mode)
     return fail("rt_renderer_set_path_lights: this configuration's shadow rays scan no light-space lists "
                 "(RT_RENDER_BVH_WALK, RT_RENDER_HOST_SETUP, RT_SHADOW_LISTS=0, no geometry)", -2);
-  if (r->deep || !(r->arg.flags & RT_FLAG_BVH4H))
+  if (r->generic_tree())
     return fail("rt_renderer_set_path_lights: pt_lights walks the binary16 BVH4 only; this tree runs the generic "
                 "(deep) images", -2);
   if (!r->set_words) return fail("rt_renderer_set_path_lights: the driver passes no launch words", -2);
-  if (!r->krnl_plights[0]) {
-    // next to the pt_kernel.vxbin in use: the kernel directory's when it holds one (a directory
-    // with a path tracer of its own and no pt_lights images, e.g. pt_compact, is refused)
-    std::string dir = r->kdir;
-    if (FILE* fk = std::fopen((dir + "/pt_kernel.vxbin").c_str(), "rb")) std::fclose(fk);
-    else dir = lib_dir();
-    const char* names[2] = {"pt_lights.vxbin", "pt_lights_accum.vxbin"};
-    for (int i = 0; i < 2; ++i)
-      if (FILE* fa = std::fopen((dir + "/" + names[i]).c_str(), "rb")) std::fclose(fa);
-      else
-        return fail("rt_renderer_set_path_lights: no " + std::string(names[i]) + " next to " + dir +
-                    "/pt_kernel.vxbin", -2);
-    for (int i = 0; i < 2; ++i)
-      if (vx_upload_kernel_file(r->dev, (dir + "/" + names[i]).c_str(), &r->krnl_plights[i]) != 0) {
-        for (int j = 0; j <= i; ++j) {
-          if (r->krnl_plights[j]) vx_mem_free(r->krnl_plights[j]);
-          r->krnl_plights[j] = nullptr;
-        }
-        return fail("cannot upload kernel " + dir + "/" + names[i]);
-      }
-  }
-  if (n == 1) {
-    // one light: rt_renderer_set_light with its lists queued at once
-    const uint32_t defer = r->sl_defer;
-    r->sl_defer = 0;
-    const int e = rt_renderer_set_light(r, lights[0]);
-    r->sl_defer = defer;
-    if (e != 0) return e;
-    return rtapp::settle_lists(r);
-  }
-  // a list set per light, each chain behind the frames in flight; then the table, in stream
-  // order ahead of every frame started after it
-  uint32_t launches = 0;
-  if (rtapp::build_light_sets(r, lights, n, true, &launches) != 0) return -1;
-  rt_lights_arg_t la{};
-  la.count = n;
-  la.slist_n = r->arg.slist_n;
-  for (uint32_t i = 0; i < n; ++i) {
-    const LightSet& l = r->lsets[i];
-    if (!l.built)
-      return fail("rt_renderer_set_path_lights: the light-space lists of light " + std::to_string(i) +
-                  " do not fit (pt_lights has no BVH shadow walk)", -2);
-    std::memcpy(la.l[i].light, l.light, sizeof(l.light));
-    la.l[i].slist_on = 1u;
-    la.l[i].sidx_addr = l.sidx_addr;
-    la.l[i].slist_addr = l.slist_addr;
-    if (((l.sidx_addr | l.slist_addr) >> 32) != 0) return fail("light-space lists above 4 GiB");
-  }
-  if (r->copy_async ? r->copy_async(r->args, &la, RT_LIGHTS_ARG_OFFSET, sizeof(la)) != 0
-                    : vx_copy_to_dev(r->args, &la, RT_LIGHTS_ARG_OFFSET, sizeof(la)) != 0)
-    return fail("light table upload failed");
-  if (vx_ready_wait(r->dev, VX_MAX_TIMEOUT) != 0) return fail("vx_ready_wait failed");
-  r->nlights = n;
-  r->lane_break = true;
-  return 0;
+  return set_several_lights(r, lights, n, rtimg::GRP_PLIGHTS, "rt_renderer_set_path_lights", true, true);
 }
 
 uint32_t rt_path_lights_resolve(const uint32_t sums[3], uint32_t k, uint32_t alpha_argb) {
@@ -949,13 +877,21 @@ int rt_scene_vis_tree(rt_scene_h s, uint32_t width, uint32_t height, float depth
 
 }  // extern "C"
 
-int rtapp::load_image(rt_renderer* r, const std::string& name, vx_buffer_h* out) {
-  std::string path = r->kdir + "/" + name;
-  if (FILE* f = std::fopen(path.c_str(), "rb")) std::fclose(f);
-  else path = lib_dir() + "/" + name;
-  if (*out) vx_mem_free(*out);
-  *out = nullptr;
-  return vx_upload_kernel_file(r->dev, path.c_str(), out) == 0 ? 0 : fail("cannot upload kernel " + path);
+int rtapp::load_images(rt_renderer* r, rtimg::Group group, const char* who) {
+  bool loaded = true;
+  for (int i = 0; i < rtimg::IMG_COUNT; ++i)
+    if (rtimg::desc((rtimg::Image)i).group == group && !r->img[i]) loaded = false;
+  if (loaded) return 0;
+  std::vector<rtimg::Found> files;
+  std::string err;
+  const int e = rtimg::resolve_group(r->kdir, lib_dir(), group, file_exists, &files, &err);
+  if (e < 0) return fail(std::string(who) + ": " + err, e);
+  for (const rtimg::Found& f : files)
+    if (!r->img[f.id] && upload_image(r, f.path, &r->img[f.id]) != 0) {
+      for (const rtimg::Found& g : files) r->free_image(g.id);
+      return -1;
+    }
+  return 0;
 }
 
 extern "C" {
@@ -963,12 +899,10 @@ extern "C" {
 namespace {
 
 // the generic RT / PT images: every BVH layout, the 32-entry traversal stack
+// (in place of the regular ones, which no frame runs from here on)
 int load_deep_images(rt_renderer* r) {
-  if (load_image(r, "rt_kernel_deep.vxbin", &r->krnl[0][0]) ||
-      load_image(r, "rt_kernel_deep_stats.vxbin", &r->krnl[0][1]) ||
-      load_image(r, "pt_kernel_deep.vxbin", &r->krnl[1][0]) ||
-      load_image(r, "pt_kernel_deep_stats.vxbin", &r->krnl[1][1]))
-    return -1;
+  for (int i = rtimg::IMG_RT; i <= rtimg::IMG_PT_STATS; ++i) r->free_image(i);
+  if (rtapp::load_images(r, rtimg::GRP_DEEP) != 0) return -1;
   r->deep = true;
   return 0;
 }
@@ -1337,7 +1271,7 @@ int rt_renderer_configure(rt_renderer_h r, const rt_render_params_t* p) {
   // queue) on the binary16 BVH4 images when env RT_PT_QUEUE=1; the default is
   // the one-kernel pt_kernel (0.155 vs 0.235 ms at config 4)
   const char* pqe = std::getenv("RT_PT_QUEUE");
-  r->pq = (p->flags & RT_RENDER_PATH) && !r->deep && (a.flags & RT_FLAG_BVH4H) && r->krnl_pq[0][0] &&
+  r->pq = (p->flags & RT_RENDER_PATH) && !r->generic_tree() && r->img[rtimg::IMG_PT_PRIMARY] &&
           r->launch_group && pqe && std::atoi(pqe) == 1;
   a.bounces = p->bounces;
   a.seed = p->seed;
@@ -1576,13 +1510,15 @@ int render_start(rt_renderer_h r, bool sync, uint32_t accum_k) {
   }
   const uint32_t f = r->params.flags;
   const int mode = (f & RT_RENDER_PATH) ? 1 : (f & RT_RENDER_FLAT) ? 2 : (f & RT_RENDER_RASTER) ? 3 : 0;
-  const int k = (f & RT_RENDER_INSTRUMENTED) && mode != 3 ? 1 : 0;
+  const rtimg::FrameIn fi{mode, (f & RT_RENDER_INSTRUMENTED) != 0, r->nlights, accum_k, r->pq,
+                          !r->sc->tail_prims.empty(), (f & RT_RENDER_BVH_WALK) != 0, r->deep,
+                          (r->arg.flags & RT_FLAG_BVH4H) != 0, r->img[rtimg::IMG_RT_BVH] != nullptr};
   // every launch of the frame carries its light (and, while the lists wait
   // for a light that stays, the switch to the BVH walk) in its launch words:
   // rt_renderer_set_light queues no copy
   // (a frame of several lights reads them from its table: neither launch-word bit)
   // (nor does a path frame of several lights, rt_renderer_set_path_lights, accumulating or not)
-  const bool multi = r->nlights >= 2 && (mode == 1 || !accum_k);
+  const bool multi = rtimg::several_lights(fi);
   uint32_t lw[4] = {0, 0, 0, 0};
   if (r->set_words && !multi) {
     std::memcpy(lw, r->arg.light, sizeof(r->arg.light));
@@ -1597,7 +1533,7 @@ int render_start(rt_renderer_h r, bool sync, uint32_t accum_k) {
   if (buf) lw[3] |= r->cbuf1_off & RT_LW_CBUF_MASK;
   if (accum_k)
     lw[3] |= ((accum_k - 1u) << RT_LW_ACCUM_K_SHIFT) | (r->accum_reset ? RT_LW_ACCUM_RESET : 0u);
-  auto start = [&](vx_buffer_h img) {
+  auto start = [&](rtimg::Image img) {
     if (r->set_words && r->set_words(r->dev, lw, 4) != 0) return false;
     uint32_t grid = 0;  // the grid asked for (0: the image's)
     if (flip && !r->lane_break) {  // a frame on a launch lane, on the overlapped frames' grid
@@ -1610,13 +1546,12 @@ int render_start(rt_renderer_h r, bool sync, uint32_t accum_k) {
       grid = g;
     }
     // the background tier: the frame's grid dealt in a geometry and a background tier by its tag
-    for (int ki = 0; ki < 2 && r->bg_ok; ++ki)
-      if (img == r->krnl[0][ki] && !accum_k) {
-        const uint32_t tg = tier_groups_of(r, ki, grid, flip && !r->lane_break);
-        if (tg != 0 && r->set_tag(r->dev, tg) != 0) return false;
-        break;
-      }
-    if (vx_start(r->dev, img, r->args) != 0) return false;
+    // (rt_kernel / rt_kernel_stats only; bg_ok is false for a deep tree)
+    if (r->bg_ok && (img == rtimg::IMG_RT || img == rtimg::IMG_RT_STATS)) {
+      const uint32_t tg = tier_groups_of(r, img - rtimg::IMG_RT, grid, flip && !r->lane_break);
+      if (tg != 0 && r->set_tag(r->dev, tg) != 0) return false;
+    }
+    if (vx_start(r->dev, r->img[img], r->args) != 0) return false;
     r->lane_break = false;
     r->prev_buf = flip ? r->cur_buf : -1;  // (a frame into the buffer in use keeps no earlier one)
     r->cur_buf = buf;
@@ -1626,25 +1561,13 @@ int render_start(rt_renderer_h r, bool sync, uint32_t accum_k) {
   if (r->set_counters &&
       r->set_counters(r->dev, (f & (RT_RENDER_COUNTERS | RT_RENDER_INSTRUMENTED)) ? 1 : 0) != 0)
     return fail("vx_hip_set_counters failed");
-  if (accum_k) return start(multi ? r->krnl_plights[1] : r->krnl_accum) ? 0 : fail("vx_start failed");
-  // a path frame of several lights: pt_lights (set_path_lights admits the one-kernel form only)
-  if (multi && mode == 1) return start(r->krnl_plights[0]) ? 0 : fail("vx_start failed");
+  const rtimg::FrameImages fr = rtimg::frame_images(fi);
+  if (fr.second == rtimg::IMG_NONE) return start(fr.first) ? 0 : fail("vx_start failed");
   // a frame of the two-kernel path tracer is one launch group of 2
-  if (mode == 1 && r->pq) {
-    if (r->launch_group(r->dev, 2) != 0) return fail("vx_hip_launch_group failed");
-    if (start(r->krnl_pq[0][k]) && start(r->krnl_pq[1][k])) return 0;
-    r->launch_group(r->dev, 0);  // abandon the half-issued group: later launches stand alone
-    return fail("vx_start failed");
-  }
-  // BVH-walk primary+shadow frames: their own image on the binary16 BVH4
-  // (the deep images walk every layout with the list code paths idle)
-  const bool bvh = mode == 0 && (f & RT_RENDER_BVH_WALK) && !r->deep && (r->arg.flags & RT_FLAG_BVH4H) &&
-                   r->krnl_bvh[k];
-  vx_buffer_h img = bvh ? r->krnl_bvh[k] : r->krnl[mode][k];
-  if (multi) img = r->krnl_lights[k];  // (set_lights admits plain shadow frames only: mode 0, no tail)
-  // a scene with an ordered tail: head traced, tail folded, one launch
-  if (mode == 0 && !r->sc->tail_prims.empty()) img = r->krnl_om;
-  return start(img) ? 0 : fail("vx_start failed");
+  if (r->launch_group(r->dev, 2) != 0) return fail("vx_hip_launch_group failed");
+  if (start(fr.first) && start(fr.second)) return 0;
+  r->launch_group(r->dev, 0);  // abandon the half-issued group: later launches stand alone
+  return fail("vx_start failed");
 }
 }  // namespace
 
@@ -1668,24 +1591,13 @@ int rt_renderer_accum_begin(rt_renderer_h r) {
     return fail("rt_renderer_accum_begin: no instrumented accumulation image (RT_RENDER_INSTRUMENTED)", -2);
   if (r->pq) return fail("rt_renderer_accum_begin: the two-kernel path queue (RT_PT_QUEUE=1) does not accumulate", -2);
   // (a scene without geometry starts no path and walks no tree: any image serves it)
-  if (r->arg.num_geom > 0 && (r->deep || !(r->arg.flags & RT_FLAG_BVH4H)))
+  if (r->arg.num_geom > 0 && r->generic_tree())
     return fail("rt_renderer_accum_begin: pt_accum walks the binary16 BVH4 only; this tree runs the generic "
                 "(deep) images", -2);
   if (!r->set_words) return fail("rt_renderer_accum_begin: the driver passes no launch words", -2);
-  if (!r->krnl_accum) {
-    // next to the pt_kernel.vxbin in use: the kernel directory's when it holds one (a
-    // directory with a path tracer of its own and no pt_accum, e.g. pt_compact, is refused)
-    std::string dir = r->kdir;
-    if (FILE* fk = std::fopen((dir + "/pt_kernel.vxbin").c_str(), "rb")) std::fclose(fk);
-    else dir = lib_dir();
-    const std::string path = dir + "/pt_accum.vxbin";
-    if (FILE* fa = std::fopen(path.c_str(), "rb")) std::fclose(fa);
-    else return fail("rt_renderer_accum_begin: no pt_accum.vxbin next to " + dir + "/pt_kernel.vxbin", -2);
-    if (vx_upload_kernel_file(r->dev, path.c_str(), &r->krnl_accum) != 0) {
-      r->krnl_accum = nullptr;
-      return fail("cannot upload kernel " + path);
-    }
-  }
+  // (next to the pt_kernel.vxbin in use: a directory with a path tracer of its own and no
+  // pt_accum, e.g. pt_compact, is refused)
+  if (const int e = rtapp::load_images(r, rtimg::GRP_ACCUM, "rt_renderer_accum_begin")) return e;
   const uint64_t bytes = r->cbuf_bytes * 4;  // 16 B per framebuffer pixel
   if (!r->accum || r->accum_bytes != bytes) {
     // (upload frees the old buffer: not under launches still writing it)
@@ -1923,7 +1835,7 @@ static int build_lbvh(rt_renderer_h r, rt_bvh_build_stats_t* st) {
   if (n == 0) return fail("no depth-tested geometry to build a BVH over");
   const auto t0 = std::chrono::steady_clock::now();
   vx_buffer_h krnl = nullptr;
-  if (load_image(r, "bvh_build.vxbin", &krnl)) return -1;
+  if (upload_image(r, rtimg::resolve_file(r->kdir, lib_dir(), "bvh_build.vxbin", file_exists), &krnl)) return -1;
   DevBuf kimg;
   kimg.h = krnl;
   // ingestion: the clip-space (x, y, w) corners, one float4 each
@@ -2065,7 +1977,7 @@ static int build_sah(rt_renderer_h r, rt_bvh_build_stats_t* st) {
   const uint32_t n = (uint32_t)s->geometry.size();
   const auto t0 = std::chrono::steady_clock::now();
   if (!r->set_tag) return fail("the driver has no vx_hip_set_launch_tag");
-  if (!r->sah_krnl && load_image(r, "bvh_sah.vxbin", &r->sah_krnl)) return -1;
+  if (rtapp::load_images(r, rtimg::GRP_SAH)) return -1;
   std::vector<float> verts((size_t)n * 12, 0.0f);
   for (uint32_t i = 0; i < n; ++i) {
     const auto& p = s->scene.prims[s->geometry[i]];
@@ -2141,7 +2053,7 @@ static int build_sah(rt_renderer_h r, rt_bvh_build_stats_t* st) {
       while (!trace && k > 1 && !(grouped = r->launch_group && r->launch_group(r->dev, k | VX_HIP_GROUP_UNTIMED) == 0))
         k >>= 1;
       for (uint32_t j = i; j < i + k; ++j) {
-        if (r->set_tag(r->dev, j) != 0 || vx_start(r->dev, r->sah_krnl, r->su.sah_args.h) != 0) {
+        if (r->set_tag(r->dev, j) != 0 || vx_start(r->dev, r->img[rtimg::IMG_SAH], r->su.sah_args.h) != 0) {
           if (grouped) r->launch_group(r->dev, 0);
           return fail("vx_start failed");
         }

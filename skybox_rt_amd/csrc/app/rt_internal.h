@@ -10,6 +10,7 @@
 #include "app_util.h"
 #include "bvh.h"
 #include "cgltrace.h"
+#include "frame_image.h"
 #include "rt_common.h"
 #include "vortex.h"
 #include "vortex_hip.h"
@@ -83,41 +84,33 @@ struct LightSet {
 struct rt_renderer {
   rt_scene* sc = nullptr;
   vx_device_h dev = nullptr;
-  // several lights (vx_rt.h rt_renderer_set_lights): rt_lights / rt_lights_stats, loaded by the
-  // first set_lights; the lights' list sets (kept across calls: their buffers only grow) and
-  // the number in use -- 0: one light, the renderer's own state, every path as before
-  vx_buffer_h krnl_lights[2] = {};
-  // a path frame under several lights (rt_renderer_set_path_lights): pt_lights, pt_lights_accum,
-  // loaded by the first call; lsets and nlights as above
-  vx_buffer_h krnl_plights[2] = {};
+  // the kernel images (frame_image.h), uploaded a group at a time by rtapp::load_images: the
+  // modes' at creation, the deep ones (then in place of the regular rt / pt ones) when a tree
+  // needs them, the others by the first call that runs them
+  vx_buffer_h img[rtimg::IMG_COUNT] = {};
+  void free_image(int i) {
+    if (img[i]) vx_mem_free(img[i]);
+    img[i] = nullptr;
+  }
+  // several lights (vx_rt.h rt_renderer_set_lights, rt_renderer_set_path_lights): the lights'
+  // list sets (kept across calls: their buffers only grow) and the number in use -- 0: one
+  // light, the renderer's own state, every path as before
   std::vector<LightSet> lsets;
   uint32_t nlights = 0;
   ListSet set0() {
     return ListSet{&sidx, &slist, &arg.sidx_addr, &arg.slist_addr, &su.scap, sl_light, &sl_built, &sl_rejected,
                    &sl_entries};
   }
-  // kernel images [mode][instrumented]: mode 0 = primary+shadow (BVH),
-  // 1 = path trace, 2 = flat list, 3 = raster (no instrumented image)
-  vx_buffer_h krnl[4][2] = {};
-  // path tracing in two kernels (the default with the binary16 BVH4): [0]
-  // pt_primary (primary pass, path queue), [1] pt_queue (the queued paths);
-  // [.][1] the instrumented images
-  vx_buffer_h krnl_pq[2][2] = {};
-  // RT_RENDER_BVH_WALK primary+shadow frames (binary16 BVH4 images only):
-  // rt_bvh / rt_bvh_stats, the packet walks without the list code paths
-  vx_buffer_h krnl_bvh[2] = {};
-  vx_buffer_h sah_krnl = nullptr;  // bvh_sah.vxbin, loaded by the first device build
-  // scenes with an ordered tail: rt_om.vxbin (plain and shadow frames), the
-  // per-block tail lists and the tail's rt_vtri_t records (host-built per configure)
-  vx_buffer_h krnl_om = nullptr, oidx = nullptr, olist = nullptr, ovtris = nullptr;
+  // scenes with an ordered tail (rt_om, plain and shadow frames): the per-block tail lists
+  // and the tail's rt_vtri_t records (host-built per configure)
+  vx_buffer_h oidx = nullptr, olist = nullptr, ovtris = nullptr;
   uint64_t olist_entries = 0;
   vx_buffer_h pathq = nullptr, pathq_ctr = nullptr;
   bool pq = false;          // the configuration runs the two-kernel path tracer
-  // progressive accumulation (vx_rt.h rt_renderer_accum_begin): pt_accum.vxbin, loaded by the
-  // first accum_begin from the directory pt_kernel.vxbin came from; the record buffer
-  // (rt_common.h rt_accum_arg_t: 16 B per framebuffer pixel) of the current configuration,
-  // named in the argument buffer behind rt_kernel_arg_t
-  vx_buffer_h krnl_accum = nullptr, accum = nullptr;
+  // progressive accumulation (vx_rt.h rt_renderer_accum_begin): the record buffer (rt_common.h
+  // rt_accum_arg_t: 16 B per framebuffer pixel) of the current configuration, named in the
+  // argument buffer behind rt_kernel_arg_t
+  vx_buffer_h accum = nullptr;
   uint64_t accum_bytes = 0;
   bool accum_on = false;     // between accum_begin and the next configure
   bool accum_reset = false;  // the next accumulation launch carries RT_LW_ACCUM_RESET
@@ -155,10 +148,10 @@ struct rt_renderer {
   uint64_t sl_entries = 0;
   vx_buffer_h gather_recv = nullptr, gather_image = nullptr;  // rank 0 of rt_render_gather
   vx_buffer_h prims = nullptr, cbuf = nullptr, args = nullptr;
-  // device-side setup (device_setup.cpp, kernels/rt_setup.hip): the image,
-  // the resolution-independent inputs uploaded once at creation, and the
+  // device-side setup (device_setup.cpp, kernels/rt_setup.hip): the
+  // resolution-independent inputs uploaded once at creation, and the
   // per-primitive visibility records of the current configuration
-  vx_buffer_h setup_krnl = nullptr, verts = nullptr, pdc = nullptr, dcz = nullptr;
+  vx_buffer_h verts = nullptr, pdc = nullptr, dcz = nullptr;
   vx_buffer_h layer_list = nullptr, geometry_list = nullptr, vis = nullptr;
   uint64_t cbuf_bytes = 0;
   // frame overlap (vx_rt.h rt_render_start): while `lanes` is set, frame n
@@ -213,6 +206,8 @@ struct rt_renderer {
   vx_hip_set_timing_t set_timing = nullptr;
   std::string kdir;         // kernel directory (images missing there come from lib_dir)
   bool deep = false;        // generic RT/PT images (every BVH layout, 32-entry stack)
+  // the configured tree runs the generic images: not the binary16 BVH4 the others walk
+  bool generic_tree() const { return rtimg::generic_tree(deep, (arg.flags & RT_FLAG_BVH4H) != 0); }
   // the primary rays' tree of the current configuration (rt_renderer_export_vis_tree;
   // host setup only -- after a device setup it is read back on request)
   std::vector<std::array<int32_t, 4>> vis_refs;
@@ -225,16 +220,12 @@ struct rt_renderer {
   rt_bvh_build_stats_t bvh_stats{};  // how the current tree was built (rt_renderer_bvh_stats)
 
   ~rt_renderer() {
-    vx_buffer_h* bufs[] = {&krnl[0][0], &krnl[0][1], &krnl[1][0], &krnl[1][1], &krnl[2][0],
-                           &krnl[2][1], &krnl[3][0], &nodes, &nodes4, &tris, &layers, &dcs, &tex,
-                           &ptris, &geom, &oms, &bbox, &zbuf, &order, &vnodes, &vtris, &vlayers,
-                           &vgeom, &gather_recv, &gather_image, &prims, &cbuf, &cbuf1, &args,
-                           &setup_krnl, &verts, &pdc, &dcz, &layer_list, &geometry_list, &vis,
-                           &blist, &bidx, &cdesc, &sidx, &slist, &krnl_pq[0][0], &krnl_pq[0][1],
-                           &krnl_pq[1][0], &krnl_pq[1][1], &pathq, &pathq_ctr,
-                           &krnl_bvh[0], &krnl_bvh[1], &sah_krnl, &krnl_om, &oidx, &olist, &ovtris,
-                           &krnl_accum, &accum, &krnl_lights[0], &krnl_lights[1],
-                           &krnl_plights[0], &krnl_plights[1]};
+    for (int i = 0; i < rtimg::IMG_COUNT; ++i) free_image(i);
+    vx_buffer_h* bufs[] = {&nodes, &nodes4, &tris, &layers, &dcs, &tex, &ptris, &geom, &oms, &bbox, &zbuf,
+                           &order, &vnodes, &vtris, &vlayers, &vgeom, &gather_recv, &gather_image, &prims,
+                           &cbuf, &cbuf1, &args, &verts, &pdc, &dcz, &layer_list, &geometry_list, &vis,
+                           &blist, &bidx, &cdesc, &sidx, &slist, &pathq, &pathq_ctr, &oidx, &olist, &ovtris,
+                           &accum};
     for (auto* b : bufs) {
       if (*b) vx_mem_free(*b);
       *b = nullptr;
@@ -259,8 +250,10 @@ int host_bvh(rt_scene* s);
 // (re)allocate *buf (size bytes, or 64 when 0), copy `data` when given; the
 // device address must lie below 4 GiB (the kernels' 32-bit arena offsets)
 int upload(vx_device_h dev, const void* data, uint64_t size, vx_buffer_h* buf, uint64_t* addr);
-// kernel image `name` from the renderer's kernel directory (else the library's)
-int load_image(rt_renderer* r, const std::string& name, vx_buffer_h* out);
+// the images of `group` (frame_image.h) that are not loaded yet, by their source rules; -2 and
+// a message "`who`: no <file> next to <anchor>" when one is not next to its anchor, -1 (and
+// none of the group loaded) when an upload fails
+int load_images(rt_renderer* r, rtimg::Group group, const char* who = "");
 
 struct DevBuf {  // scratch buffer freed at scope exit
   vx_buffer_h h = nullptr;
