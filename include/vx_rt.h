@@ -479,6 +479,69 @@ int rt_renderer_set_path_lights(rt_renderer_h r, const float (*lights)[3], uint3
  * outside 1..RT_MAX_PATH_LIGHTS or a sum above 255 * k: the alpha byte alone */
 uint32_t rt_path_lights_resolve(const uint32_t sums[3], uint32_t k, uint32_t alpha_argb);
 
+/* Per-pixel visibility records of a primary+shadow frame, in one launch.  NO
+ * REFERENCE (the reference returns colours only; the oracle's rt_render gives
+ * pid and t per pixel, its raster_render the depth words, and the records are
+ * held to both bit for bit).
+ *
+ * What a frame resolves per pixel and drops at its store: one 16-byte record
+ * per framebuffer pixel, at the pixel's framebuffer index -- linear W * H, or
+ * for compact / sharded configurations local_tiles * 1024 in task order,
+ * exactly as rt_read_framebuffer orders pixels.  The launch (image rt_aov,
+ * kernels/rt_aov_kernel.hip) does primary visibility, the layer resolve and
+ * one shadow ray per light in use, in place; it shades nothing and reads no
+ * texel.  A k-light frame's pixel is a pure function of the unshadowed
+ * frame's pixel and the record's mask (rt_aov_relight), so a client may dim,
+ * colour or switch off single lights without rendering again.
+ *
+ * The lights in use: one light after rt_renderer_configure or
+ * rt_renderer_set_light -- the argument block and the launch words exactly as
+ * a frame has them: a moved light whose lists are deferred or stale walks the
+ * BVH and gives the same verdicts -- and n lights after
+ * rt_renderer_set_lights, each on its own lists or, where it has none, by the
+ * BVH packet walk.
+ *
+ * rt_render_aov_start: valid on a configured primary+shadow-family frame --
+ * with or without RT_RENDER_SHADOWS (without: masks and RT_AOV_SHADOW_RAY all
+ * zero), RT_RENDER_BVH_WALK, COUNTERS, COMPACT, shards and HOST_SETUP as
+ * usual.  -2 (rt_last_error says why) for RT_RENDER_PATH, FLAT, RASTER or
+ * INSTRUMENTED, a scene with a non-empty ordered tail (RT_SCENE_OM_LAYERS), a
+ * tree the generic (deep) images run.  The image (rt_aov.vxbin: the kernel
+ * directory's, else the library's) is loaded by the first call and kept for
+ * the renderer's life; the record buffer is allocated by the first call after
+ * a configure (rt_renderer_configure and rt_renderer_free release it); later
+ * calls queue one launch and no copy.  An ordinary launch, as an accumulation
+ * launch is: no launch lane, the image's own grid, behind the frames in
+ * flight on both lanes and ahead of everything started after it.  It writes
+ * only its own buffer -- rt_read_framebuffer still returns the last frame --
+ * rt_render_wait covers it, and rt_render_stats / rt_render_kernel_ms after
+ * it describe it: with RT_RENDER_COUNTERS primary_rays and geometry_hits are
+ * a frame's, shadow_rays is the sum over the lights and occluded the sum of
+ * the masks' set bits. */
+#define RT_AOV_GEOM 0x01000000u
+#define RT_AOV_SHADOW_RAY 0x02000000u
+typedef struct {
+  int32_t  pid;          /* the shaded primitive: the depth-tested winner, else the last drawn
+                            covering screen layer, else -1 (the oracle's rt_render pid) */
+  uint32_t depth_flags;  /* bits 0-23: the winner's depth word (0xffffff without a geometry hit)
+                            -- the raster pipeline's depth & 0xffffff; bit 24 RT_AOV_GEOM: a
+                            geometry hit; bit 25 RT_AOV_SHADOW_RAY: shadow rays start here
+                            (RT_RENDER_SHADOWS, a geometry hit, plane t finite and > 0); bits
+                            26-31 zero */
+  float    t;            /* plane t of the geometry winner as computed (also when not finite or
+                            <= 0: then no shadow ray); 0 without a geometry hit (the oracle's t) */
+  uint32_t light_mask;   /* bit i: light i of the lights in use does NOT see the pixel (its shadow
+                            ray is occluded); 0 without RT_AOV_SHADOW_RAY; bits >= the light count 0 */
+} rt_aov_t;
+int rt_render_aov_start(rt_renderer_h r);   /* one launch, no host wait once image and buffer exist */
+int rt_render_aov(rt_renderer_h r);         /* start + wait */
+/* the records in framebuffer order, count >= the framebuffer's pixels (waits for the device) */
+int rt_read_aov(rt_renderer_h r, rt_aov_t* out, uint64_t count);
+/* = rt_lights_resolve(plain_argb, popcount(light_mask & (2^k - 1)), k): the k-light frame's
+ * pixel from the unshadowed frame's pixel and the record's mask (k outside 1..RT_MAX_LIGHTS:
+ * plain_argb) */
+uint32_t rt_aov_relight(uint32_t plain_argb, uint32_t light_mask, uint32_t k);
+
 /* Read back one per-resolution record array of the current configuration
  * (layouts: kernels/rt_common.h; NO REFERENCE).  out NULL = size query
  * (*size = bytes). */

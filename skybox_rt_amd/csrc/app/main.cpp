@@ -26,7 +26,12 @@
 // same: its head traced, its ordered tail folded through the output merger,
 // vx_rt.h); -A samples, with -P: that many samples per pixel accumulated on
 // the device (rt_render_accumulate: launches of 32, then one for the rest)
-// and their mean written, -r comparing as usual; multi-GPU (one process per GPU over
+// and their mean written, -r comparing as usual; -V file: after the frame one
+// visibility-record launch (rt_render_aov) of the same configuration and
+// lights, written as a 16-byte header ('RTAV', width, height, 16) and the
+// rt_aov_t records in framebuffer order (with -G: this rank's compact tiles),
+// and one line "AOV: <geometry pixels> geometry, <shadow rays> shadow rays,
+// <occluded> occluded"; multi-GPU (one process per GPU over
 // librt_shard.so / RCCL): -G rank,ranks -I idfile -- this process renders
 // 32x32 tiles t with t % ranks == rank, rank 0 writes the RCCL communicator
 // id to `idfile` (the others wait for it), every frame ends with
@@ -75,6 +80,7 @@ bool host_setup = false;              // -H: per-resolution records by the host 
 bool om_layers = false;               // -O: RT_SCENE_OM_LAYERS
 uint32_t accum_samples = 0;           // -A: with -P, accumulate this many samples per pixel
 std::vector<std::array<float, 3>> more_lights;  // -M: lights beside the one of -L
+const char* aov_file = nullptr;       // -V: write the frame's visibility records
 
 #ifdef RT_APP_RASTER
 const char* kOpts = "t:i:o:r:w:h:k:n:z?";
@@ -84,7 +90,7 @@ void usage() {
               "[-k tilelogsize] [-n repeat]\n");
 }
 #else
-const char* kOpts = "t:s:e:i:o:r:w:h:k:n:L:M:P:G:I:B:A:uxyzSRFHO?";
+const char* kOpts = "t:s:e:i:o:r:w:h:k:n:L:M:P:G:I:B:A:V:uxyzSRFHO?";
 void usage() {
   std::printf("Vortex 3D Rendering Test (MI355X).\n"
               "Usage: [-t trace] [-s startdraw] [-e enddraw] [-o output] [-r reference] [-w width] "
@@ -94,6 +100,7 @@ void usage() {
               "       [-O trace the head, fold blended / stencil / masked drawcalls (RT_SCENE_OM_LAYERS)]\n"
               "       [-A samples: with -P, accumulate that many samples per pixel on the device and "
               "write their mean]\n"
+              "       [-V file: the frame's per-pixel visibility records (primary + shadow frames)]\n"
               "       env RT_KERNEL_DIR: kernel images; RT_ASSETS_PATHS: search directories\n");
 }
 #endif
@@ -141,6 +148,7 @@ int main(int argc, char** argv) {
     case 'H': host_setup = true; break;
     case 'O': om_layers = true; break;
     case 'A': accum_samples = (uint32_t)std::atoi(optarg); break;
+    case 'V': aov_file = optarg; break;
 #endif
     case '?': usage(); return 0;
     default: usage(); return -1;  // -i: in the reference's option string, never handled
@@ -327,6 +335,25 @@ int main(int argc, char** argv) {
                 total / repeat, st.grid, st.block, rays, (unsigned long long)st.primary_rays,
                 (unsigned long long)st.shadow_rays, (unsigned long long)st.bounce_rays,
                 (unsigned long long)st.occluded, rays / (total / repeat) * 1e-3);
+  }
+  if (aov_file) {
+    // the visibility records of the frame just rendered: one more launch, its own buffer
+    rt_stats_t as;
+    RT_CHECK(rt_render_aov(r));
+    RT_CHECK(rt_render_stats(r, &as));
+    std::vector<rt_aov_t> rec(sharded ? (size_t)as.local_tiles * 1024u : (size_t)width * height);
+    RT_CHECK(rt_read_aov(r, rec.data(), rec.size()));
+    const uint32_t head[4] = {0x56415452u /* 'RTAV' */, width, height, (uint32_t)sizeof(rt_aov_t)};
+    std::ofstream f(aov_file, std::ios::binary);
+    f.write((const char*)head, sizeof(head));
+    f.write((const char*)rec.data(), (std::streamsize)(rec.size() * sizeof(rt_aov_t)));
+    f.close();
+    if (!f) {
+      std::printf("Error: cannot write %s\n", aov_file);
+      return 1;
+    }
+    std::printf("AOV: %llu geometry, %llu shadow rays, %llu occluded\n", (unsigned long long)as.geometry_hits,
+                (unsigned long long)as.shadow_rays, (unsigned long long)as.occluded);
   }
   int errors = 0;
   if (std::strcmp(output_file, "null") != 0 && (!sharded || rank == 0)) {

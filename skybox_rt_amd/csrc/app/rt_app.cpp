@@ -1209,6 +1209,13 @@ int rt_renderer_configure(rt_renderer_h r, const rt_render_params_t* p) {
   r->accum_on = r->accum_reset = false;
   r->accum_bytes = 0;
   r->accum_n = 0;
+  // and releases the visibility records (rt_render_aov_start), the same way
+  if (r->aov) {
+    if (vx_ready_wait(r->dev, VX_MAX_TIMEOUT) != 0) return fail("vx_ready_wait failed");
+    vx_mem_free(r->aov);
+    r->aov = nullptr;
+  }
+  r->aov_bytes = 0;
   r->nlights = 0;  // a configure returns to one light (rt_renderer_set_lights)
   rt_kernel_arg_t& a = r->arg;
   a.width = p->width;
@@ -1432,8 +1439,9 @@ int rt_renderer_configure(rt_renderer_h r, const rt_render_params_t* p) {
   // (behind the block, the accumulating path tracer's area: rt_renderer_accum_begin writes it)
   // (and behind that the background tier's: rt_tier_arg_t, constant until the next configure)
   // (and the light table of rt_renderer_set_lights)
+  // (and the visibility records' area: rt_render_aov_start writes it)
   if (!r->args &&
-      upload(r->dev, nullptr, RT_LIGHTS_ARG_OFFSET + sizeof(rt_lights_arg_t), &r->args, &args_addr))
+      upload(r->dev, nullptr, RT_AOV_ARG_OFFSET + sizeof(rt_aov_arg_t), &r->args, &args_addr))
     return -1;
   if (r->copy_async ? r->copy_async(r->args, &a, 0, sizeof(a)) != 0
                     : vx_copy_to_dev(r->args, &a, 0, sizeof(a)) != 0)
@@ -1669,6 +1677,78 @@ uint32_t rt_accum_resolve(const uint32_t rec[4], uint32_t alpha_argb) {
     c |= (uint32_t)(m > 255 ? 255 : m) << (16 - 8 * k);
   }
   return c;
+}
+
+// ---- per-pixel visibility records (vx_rt.h; NO REFERENCE) -----------------
+
+static_assert(sizeof(rt_aov_t) == 16, "one 16-byte record per pixel");
+
+int rt_render_aov_start(rt_renderer_h r) {
+  if (!r || !r->configured) return fail("renderer not configured");
+  const uint32_t f = r->params.flags;
+  if (f & (RT_RENDER_PATH | RT_RENDER_FLAT | RT_RENDER_RASTER | RT_RENDER_INSTRUMENTED))
+    return fail("rt_render_aov: a primary+shadow frame only (no RT_RENDER_PATH / FLAT / RASTER / INSTRUMENTED)", -2);
+  if (!r->sc->tail_prims.empty())
+    return fail("rt_render_aov: a scene with an ordered tail has no visibility records (its tail's fragments are "
+                "merged, not traced)", -2);
+  // (a scene without geometry traces no shadow ray and walks no tree: any image serves it)
+  if (r->arg.num_geom > 0 && r->generic_tree())
+    return fail("rt_render_aov: rt_aov walks the binary16 BVH4 only; this tree runs the generic (deep) images", -2);
+  const uint32_t nl = r->nlights >= 2 ? r->nlights : 0u;
+  if (nl != 0 && !r->set_tag) return fail("rt_render_aov: the driver passes no launch tag (several lights)", -2);
+  // the image, by the per-file rule: the kernel directory's file, else the library's
+  if (!r->aov_img &&
+      upload_image(r, rtimg::resolve_file(r->kdir, lib_dir(), "rt_aov.vxbin", file_exists), &r->aov_img))
+    return -1;
+  const uint64_t bytes = r->cbuf_bytes * 4;  // 16 B per framebuffer pixel
+  if (!r->aov || r->aov_bytes != bytes) {
+    // (upload frees the old buffer: not under launches still writing it)
+    if (r->aov && vx_ready_wait(r->dev, VX_MAX_TIMEOUT) != 0) return fail("vx_ready_wait failed");
+    uint64_t addr = 0;
+    r->aov_bytes = 0;
+    if (upload(r->dev, nullptr, bytes, &r->aov, &addr)) return -1;
+    r->aov_bytes = bytes;
+    rt_aov_arg_t aa{};
+    aa.aov_addr = addr;
+    // behind the launches in flight (they read the areas in front), ahead of every launch started after it
+    if (r->copy_async ? r->copy_async(r->args, &aa, RT_AOV_ARG_OFFSET, sizeof(aa)) != 0
+                      : vx_copy_to_dev(r->args, &aa, RT_AOV_ARG_OFFSET, sizeof(aa)) != 0)
+      return fail("visibility record argument upload failed");
+  }
+  // one light: the light (and, while its lists wait for a light that stays, the switch to the BVH
+  // walk) in the launch words, as a frame carries them; several: the table, their number the tag
+  uint32_t lw[4] = {0, 0, 0, 0};
+  if (r->set_words && nl == 0) {
+    std::memcpy(lw, r->arg.light, sizeof(r->arg.light));
+    lw[3] = RT_LW_LIGHT | (r->sl_stale ? RT_LW_NO_SLIST : 0u);
+  }
+  if (r->set_counters && r->set_counters(r->dev, (f & RT_RENDER_COUNTERS) ? 1 : 0) != 0)
+    return fail("vx_hip_set_counters failed");
+  if (r->set_words && r->set_words(r->dev, lw, 4) != 0) return fail("vx_hip_set_launch_words failed");
+  if (nl != 0 && r->set_tag(r->dev, nl) != 0) return fail("vx_hip_set_launch_tag failed");
+  // an ordinary launch (no lane asked for) on the image's own grid: the driver orders it behind
+  // the frames in flight on both lanes and ahead of what starts after it
+  if (vx_start(r->dev, r->aov_img, r->args) != 0) return fail("vx_start failed");
+  return 0;
+}
+
+int rt_render_aov(rt_renderer_h r) {
+  const int e = rt_render_aov_start(r);
+  return e ? e : rt_render_wait(r);
+}
+
+int rt_read_aov(rt_renderer_h r, rt_aov_t* out, uint64_t count) {
+  if (!r || !out || !r->configured) return fail("renderer not configured");
+  if (!r->aov) return fail("rt_read_aov: no visibility records (rt_render_aov)", -2);
+  if (count * sizeof(rt_aov_t) < r->aov_bytes) return fail("buffer too small");
+  // (a shard without a tile has no record)
+  return (r->aov_bytes == 0 || vx_copy_from_dev(out, r->aov, 0, r->aov_bytes) == 0) ? 0
+                                                                                   : fail("vx_copy_from_dev failed");
+}
+
+uint32_t rt_aov_relight(uint32_t plain_argb, uint32_t light_mask, uint32_t k) {
+  if (k < 1 || k > RT_MAX_LIGHTS) return plain_argb;
+  return rt_lights_mix(plain_argb, (uint32_t)__builtin_popcount(light_mask & ((1u << k) - 1u)), k);
 }
 
 int rt_render_stats(rt_renderer_h r, rt_stats_t* st) {

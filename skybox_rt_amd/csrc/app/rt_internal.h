@@ -115,6 +115,12 @@ struct rt_renderer {
   bool accum_on = false;     // between accum_begin and the next configure
   bool accum_reset = false;  // the next accumulation launch carries RT_LW_ACCUM_RESET
   uint32_t accum_n = 0;      // samples queued since the last reset: the records' n once they ran
+  // visibility records (vx_rt.h rt_render_aov_start): the rt_aov image, loaded by the first call
+  // that runs it and kept for the renderer's life -- not an image a frame runs, so not in img[]
+  // -- and the record buffer of the current configuration (rt_common.h rt_aov_arg_t: 16 B per
+  // framebuffer pixel), named in the argument buffer behind the light table
+  vx_buffer_h aov_img = nullptr, aov = nullptr;
+  uint64_t aov_bytes = 0;
   vx_buffer_h nodes = nullptr, nodes4 = nullptr, tris = nullptr, layers = nullptr, dcs = nullptr, tex = nullptr;
   vx_buffer_h ptris = nullptr, geom = nullptr, oms = nullptr, bbox = nullptr, zbuf = nullptr;
   vx_buffer_h order = nullptr;
@@ -225,7 +231,7 @@ struct rt_renderer {
                            &order, &vnodes, &vtris, &vlayers, &vgeom, &gather_recv, &gather_image, &prims,
                            &cbuf, &cbuf1, &args, &verts, &pdc, &dcz, &layer_list, &geometry_list, &vis,
                            &blist, &bidx, &cdesc, &sidx, &slist, &pathq, &pathq_ctr, &oidx, &olist, &ovtris,
-                           &accum};
+                           &accum, &aov, &aov_img};
     for (auto* b : bufs) {
       if (*b) vx_mem_free(*b);
       *b = nullptr;

@@ -1,0 +1,150 @@
+// rt_aov_kernel.hip -- the per-pixel visibility records of a primary+shadow
+// frame (vx_rt.h rt_render_aov_start, rt_aov_t): what rt_kernel resolves per
+// pixel and drops at its store -- the shaded primitive, the winner's 24-bit
+// depth word, the plane t its secondary rays start at, and per light whether
+// the light sees the point -- written as one 16-byte record per framebuffer
+// pixel, at the pixel's framebuffer index, into a buffer of the launch's own.
+// No shading: no shade_wave, no texel reads, no shading-record traffic.
+//
+// One wave per 8x8 block on rt_kernel's task map (chunk_map / chunk_pixel:
+// linear, compact and sharded output alike).  The pixel stays in its lane from
+// the primary test to the store, so the shadow rays are traced in place under
+// the lane mask (rt_om_kernel.hip's pattern), not through rt_kernel's LDS
+// compaction queue: a wave-uniform loop over the lights in use, each light's
+// ray on that light's own light-space lists (occluded_list) or, where a light
+// has none, as one packet walking the binary16 BVH4 (occluded_packet).  The
+// verdicts are the frames': both tests answer "any occluder on the segment".
+//
+// The lights in use: the launch's tag n.  n < 2: the argument block's light
+// and lists under the launch words, exactly as a frame reads them (load_scene:
+// RT_LW_LIGHT, RT_LW_NO_SLIST).  n >= 2: the first n entries of the light
+// table behind the argument block (rt_common.h rt_lights_arg_t), read through
+// the scalar cache.  The record buffer's address stands behind the table
+// (rt_aov_arg_t).
+//
+// Image rt_aov (Makefile): the binary16 BVH4 only (RT_ONLY_BVH4H), built with
+// RT_LIGHTS for rt_trace.h's shadow_ray / occluded_list forms that take the
+// light and its lists as parameters.
+#include <hip/hip_runtime.h>
+
+#ifndef RT_BLOCK_THREADS
+#define RT_BLOCK_THREADS 64
+#endif
+#define VX_BLOCK_THREADS RT_BLOCK_THREADS  // vx_spawn.h: the workgroup size as a constant
+#include "rt_trace.h"
+
+#if !RT_ONLY_BVH4H || !RT_LIGHTS
+#error "rt_aov_kernel.hip walks the binary16 BVH4 only, with the light-parameter forms (build with -DRT_ONLY_BVH4H=1 -DRT_LIGHTS=1)"
+#endif
+
+namespace {
+
+using namespace rtk;
+
+// the record buffer as an arena offset (rt_app checks it lies below 4 GiB)
+__device__ __forceinline__ uint32_t aov_base(const Scene& S) {
+  uint64_t p = S.argp + RT_AOV_ARG_OFFSET;
+  asm volatile("" : "+s"(p));
+  return (uint32_t)((const __attribute__((address_space(4))) rt_aov_arg_t*)p)->aov_addr;
+}
+
+// The winner's depth word after the packet walk of the tree (no block lists),
+// which returns the pid only: the word vis_test computed for it, from the same
+// edge functions and z attribute (rt_om_kernel.hip winner_depth).
+__device__ __forceinline__ uint32_t winner_depth(const Scene& S, int32_t hit, uint32_t x, uint32_t y) {
+  if (hit < 0) return VX_OM_DEPTH_MASK;
+  const uint32_t o = S.prims + 128u * (uint32_t)hit;
+  const uint4 A = S.A.ld_u4(o), B = S.A.ld_u4(o + 16), C = S.A.ld_u4(o + 32);
+  const int32_t e0[3] = {(int32_t)A.x, (int32_t)A.y, (int32_t)A.z};
+  const int32_t e1[3] = {(int32_t)A.w, (int32_t)B.x, (int32_t)B.y};
+  const int32_t e2[3] = {(int32_t)B.z, (int32_t)B.w, (int32_t)C.x};
+  const int32_t z3[3] = {(int32_t)C.y, (int32_t)C.z, (int32_t)C.w};
+  return vis_depth(gfx::edge_eval(e0, x, y), gfx::edge_eval(e1, x, y), gfx::edge_eval(e2, x, y), z3);
+}
+
+// one light's verdict for the wave's shadow rays: true where the light does not see the lane's point
+__device__ __forceinline__ bool light_occluded(const Scene& S, const Ray& p, float th, const float L[3],
+                                               bool shadow, int32_t hit, uint32_t slist_on, uint32_t sidx,
+                                               uint32_t slist, uint32_t slist_n, Counters& cnt) {
+  Ray s;
+  shadow_ray(S, p, th, s, L);
+  cnt.shadow += shadow;
+  const bool occ = rt_usgpr(slist_on) ? occluded_list(S, s, shadow, hit, cnt, sidx, slist, slist_n)
+                                      : occluded_packet(walk_scene(S), s, shadow, hit, 1.0f, cnt);
+  return shadow && occ;
+}
+
+__device__ __forceinline__ void kernel_body(const vx_task_t& task, const Scene& S, uint32_t nl, uint32_t aov,
+                                            Counters& cnt) {
+  const uint32_t t = task.blockIdx.x;
+  // the chunk's task map in scalar registers (every lane runs the same chunk)
+  const uint32_t c = (uint32_t)__builtin_amdgcn_readfirstlane(t) >> 6;
+  const ChunkMap cm = chunk_map(S, task_args(S), c);
+  uint32_t x, y, out;
+  chunk_pixel(S, cm, t & 63u, &x, &y, &out);
+  const uint32_t lb = (cm.lt << 4) | cm.blk;
+  const bool in = x < S.width && y < S.height;  // edge tiles overhang the image
+  cnt.primary += in;
+  const bool tie_high = (S.flags & RT_FLAG_TIE_HIGH) != 0;
+
+  // primary visibility, the winner's depth word kept
+  int32_t hit;
+  uint32_t hz;
+  if (rt_usgpr(S.blist_blocks)) {
+    hit = block_primary_z(S, block_header(S, lb), x, y, in, tie_high, cnt, &hz);
+  } else {
+    const int32_t h = trace_primary_packet(walk_scene(S), x, y, in, tie_high, cnt);
+    hit = in ? h : -1;
+    hz = winner_depth(S, hit, x, y);
+  }
+  cnt.hits += hit >= 0;
+  const int32_t spid = resolve_layers(S, x, y, in && hit < 0, hit, cnt);
+
+  float th = 0.0f;
+  uint32_t df = hz | (hit >= 0 ? RT_AOV_GEOM : 0u), mask = 0;
+  if (__ballot(hit >= 0) != 0) {
+    Ray r;
+    primary_dir(S, x, y, r);
+    th = hit >= 0 ? plane_t(S, r, hit) : 0.0f;
+    const bool shadow = hit >= 0 && secondary_ok(th) && (rt_usgpr(S.flags) & RT_FLAG_SHADOWS) != 0;
+    if (__ballot(shadow) != 0) {
+      df |= shadow ? RT_AOV_SHADOW_RAY : 0u;
+      if (nl < 2) {
+        const float L[3] = {S.light[0], S.light[1], S.light[2]};
+        mask = light_occluded(S, r, th, L, shadow, hit, S.slist_on, S.sidx, S.slist, S.slist_n, cnt) ? 1u : 0u;
+      } else {
+        // (a lane some light does not see stays in the packet for the lights after it)
+        const auto* LA = lights_args(S);
+        const uint32_t sn = LA->slist_n;
+        for (uint32_t i = 0; i < nl; ++i) {
+          const float L[3] = {LA->l[i].light[0], LA->l[i].light[1], LA->l[i].light[2]};
+          const bool occ = light_occluded(S, r, th, L, shadow, hit, LA->l[i].slist_on, (uint32_t)LA->l[i].sidx_addr,
+                                          (uint32_t)LA->l[i].slist_addr, sn, cnt);
+          mask |= occ ? 1u << i : 0u;
+        }
+      }
+      cnt.occluded += (uint32_t)__popc(mask);
+    }
+  }
+  if (in) S.A.st_u4(aov + 16u * out, make_uint4((uint32_t)spid, df, __float_as_uint(th), mask));
+}
+
+__device__ __forceinline__ void flush(int slot, uint32_t v) { vx_mpm_add(RT_MPM_USER + slot, v); }
+
+}  // namespace
+
+VX_MAIN(rt_kernel_arg_t, arg, RT_BLOCK_THREADS) {
+  Counters cnt;
+  Scene S = load_scene(arg, vx_launch_words);
+  // (the tag is a kernel argument: the light count and the buffer stay in scalar registers)
+  const uint32_t nl = vx_launch_tag < RT_MAX_LIGHTS ? vx_launch_tag : RT_MAX_LIGHTS;
+  const uint32_t aov = aov_base(S);
+  const int rc = vx_spawn_tasks(
+      S.num_tasks, [&](const vx_task_t& task, const Scene* s) { kernel_body(task, *s, nl, aov, cnt); }, &S);
+  // a frame's primary rays and hits; the shadow rays of every light, the masks' set bits
+  flush(RT_STAT_PRIMARY, cnt.primary);
+  flush(RT_STAT_SHADOW, cnt.shadow);
+  flush(RT_STAT_HITS, cnt.hits);
+  flush(RT_STAT_OCCLUDED, cnt.occluded);
+  return rc;
+}

@@ -282,6 +282,21 @@ typedef struct {
   rt_light_t l[RT_MAX_LIGHTS];
 } rt_lights_arg_t;
 #define RT_LIGHTS_ARG_OFFSET (RT_TIER_ARG_OFFSET + sizeof(rt_tier_arg_t))
+// The visibility-record launch's argument area (rt_aov_kernel.hip, image rt_aov; vx_rt.h
+// rt_render_aov_start), behind the four above, which stay where they are: the record buffer, one
+// 16-B rt_aov_t {pid, depth word | flags, plane t, light mask} per framebuffer pixel at the
+// pixel's framebuffer index.  Written when the buffer is allocated, in stream order: the frames
+// in flight read the areas in front of it.  The number of lights in use is the launch's tag
+// (0 or 1: the argument block's light and lists under the launch words, as a frame; n >= 2: the
+// first n entries of the light table).
+typedef struct {
+  uint64_t aov_addr;
+  uint64_t pad;
+} rt_aov_arg_t;
+#define RT_AOV_ARG_OFFSET (RT_LIGHTS_ARG_OFFSET + sizeof(rt_lights_arg_t))
+// rt_aov_t::depth_flags above the 24-bit depth word (vx_rt.h names the same bits)
+#define RT_AOV_GEOM       0x01000000u  // a geometry hit
+#define RT_AOV_SHADOW_RAY 0x02000000u  // shadow rays start at the pixel
 // The pixel of a shadow ray that `occluded` of its k lights (1 <= k <= RT_MAX_LIGHTS) do not
 // see: per channel the rounded mean of the k single-light values, c for a light that sees it
 // and c >> 1 (shadowed()) for one that does not -- sum = (k - o) * c + o * (c >> 1), mean =

@@ -82,6 +82,11 @@ class LightInfo(C.Structure):
 
 RT_MAX_LIGHTS = 16
 RT_MAX_PATH_LIGHTS = 8
+# rt_aov_t (vx_rt.h): one visibility record per framebuffer pixel
+AOV_DTYPE = np.dtype([("pid", "<i4"), ("depth_flags", "<u4"), ("t", "<f4"), ("light_mask", "<u4")])
+RT_AOV_DEPTH_MASK = 0xFFFFFF
+RT_AOV_GEOM = 0x01000000
+RT_AOV_SHADOW_RAY = 0x02000000
 
 
 class RenderParams(C.Structure):
@@ -169,6 +174,9 @@ def lib():
             "rt_renderer_set_path_lights": [vp, vp, u32],
             "rt_renderer_lights_info": [vp, C.POINTER(LightInfo), u32, C.POINTER(u32)],
             "rt_renderer_export_light_lists": [vp, u32, u32, vp, u64, C.POINTER(u64)],
+            "rt_render_aov_start": [vp],
+            "rt_render_aov": [vp],
+            "rt_read_aov": [vp, vp, u64],
         }
         for name, argtypes in sig.items():
             fn = getattr(h, name)
@@ -180,6 +188,8 @@ def lib():
         h.rt_lights_resolve.restype = u32
         h.rt_path_lights_resolve.argtypes = [C.POINTER(u32), u32, u32]
         h.rt_path_lights_resolve.restype = u32
+        h.rt_aov_relight.argtypes = [u32, u32, u32]
+        h.rt_aov_relight.restype = u32
         h.rt_last_error.restype = C.c_char_p
         h.rt_last_error.argtypes = []
         _h = h
@@ -554,6 +564,36 @@ class Renderer:
         _check(lib().rt_read_accum(self._h, out.ctypes.data, p.height * p.width), "rt_read_accum")
         return out
 
+    # per-pixel visibility records (vx_rt.h rt_render_aov_start; image rt_aov)
+    def aov(self, wait: bool = True):
+        """One launch writing a visibility record per framebuffer pixel of the
+        configured primary+shadow frame -- the shaded primitive, the winner's
+        depth word and flags, the plane t, and per light in use whether it does
+        NOT see the pixel -- with no shading and no texel reads; the framebuffer
+        keeps the last frame.  Returns the records as a structured array
+        (AOV_DTYPE) [H, W], or [local_tiles * 1024] in the compact framebuffer's
+        order for compact / sharded frames.  wait=False: queued only, returns
+        None (wait(), then aov_records())."""
+        if not wait:
+            _check(lib().rt_render_aov_start(self._h), "rt_render_aov_start")
+            return None
+        _check(lib().rt_render_aov(self._h), "rt_render_aov")
+        return self.aov_records()
+
+    def aov_records(self) -> np.ndarray:
+        """The records of the last aov() launch (waits for the device)."""
+        p = self.params
+        if p is None:
+            raise RtError("rt_read_aov failed: renderer not configured")
+        if p.shard_count > 1 or p.flags & RT_RENDER_COMPACT:
+            n = self.stats()["local_tiles"] * TILE * TILE
+            out = np.zeros(max(n, 1), AOV_DTYPE)
+            _check(lib().rt_read_aov(self._h, out.ctypes.data, n), "rt_read_aov")
+            return out[:n]
+        out = np.zeros((p.height, p.width), AOV_DTYPE)
+        _check(lib().rt_read_aov(self._h, out.ctypes.data, out.size), "rt_read_aov")
+        return out
+
     def stats(self) -> dict:
         s = Stats()
         _check(lib().rt_render_stats(self._h, C.byref(s)), "rt_render_stats")
@@ -665,6 +705,22 @@ def lights_resolve(argb: int, occluded: int, k: int) -> int:
     `occluded` of its k lights do not see -- per channel (2 * sum + k) // (2 * k),
     sum = (k - occluded) * c + occluded * (c >> 1); argb's alpha."""
     return int(lib().rt_lights_resolve(int(argb) & 0xFFFFFFFF, int(occluded), int(k)))
+
+
+def aov_relight(plain_argb, light_mask, k: int):
+    """rt_aov_relight: the k-light frame's pixel from the unshadowed frame's
+    pixel and a visibility record's light_mask -- rt_lights_resolve(plain_argb,
+    popcount(light_mask & (2^k - 1)), k); mask bits at or above k are ignored.
+    Scalars give an int; arrays (broadcast against each other) a uint32 array,
+    the library's function applied to every distinct (pixel, mask) pair."""
+    fn = lib().rt_aov_relight
+    if np.ndim(plain_argb) == 0 and np.ndim(light_mask) == 0:
+        return int(fn(int(plain_argb) & 0xFFFFFFFF, int(light_mask) & 0xFFFFFFFF, int(k)))
+    a, m = np.broadcast_arrays(np.asarray(plain_argb).astype(np.uint32), np.asarray(light_mask).astype(np.uint32))
+    key = (a.astype(np.uint64) << np.uint64(32)) | m.astype(np.uint64)
+    uniq, inv = np.unique(key.reshape(-1), return_inverse=True)
+    vals = np.array([fn(int(u >> np.uint64(32)), int(u & np.uint64(0xFFFFFFFF)), int(k)) for u in uniq], np.uint32)
+    return vals[inv.reshape(-1)].reshape(a.shape)
 
 
 def path_lights_resolve(sums, k: int, alpha_argb: int) -> int:
