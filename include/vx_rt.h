@@ -542,6 +542,64 @@ int rt_read_aov(rt_renderer_h r, rt_aov_t* out, uint64_t count);
  * plain_argb) */
 uint32_t rt_aov_relight(uint32_t plain_argb, uint32_t light_mask, uint32_t k);
 
+/* Relighting a frame on the device from its visibility records.  NO REFERENCE
+ * (the relit frame is defined from the oracle's single-light frames and held
+ * to them bit for bit).
+ *
+ * Two launches.  The capture (image rt_aov_base: kernels/rt_aov_kernel.hip
+ * built with RT_AOV_BASE) is the record launch above -- the same records, bit
+ * for bit, in the same record buffer (rt_read_aov returns them) -- that also
+ * shades every pixel without shadows and stores that ARGB word, the pixel's
+ * base colour, into a buffer of 4 B per framebuffer pixel in framebuffer order:
+ * by definition the pixel of the same configuration's frame without
+ * RT_RENDER_SHADOWS.  The relight (image rt_relight, kernels/
+ * rt_relight_kernel.hip) is a streaming pass with no scene and no tracing: per
+ * framebuffer pixel it reads the record and the base colour and writes the
+ * relit pixel into the framebuffer in use.
+ *
+ * The relit pixel.  n = the lights in use at capture time (1 after
+ * rt_renderer_configure / rt_renderer_set_light, k after
+ * rt_renderer_set_lights); light i weighs w_i in 0..255; W = sum of the w_i;
+ * O = sum of the w_i of the lights whose bit in light_mask is set (bits at or
+ * above n are ignored).  A pixel with RT_AOV_SHADOW_RAY is, per colour channel
+ * c of its base colour, (2 * ((W - O) * c + O * (c >> 1)) + W) / (2 * W) in
+ * integer division -- the weighted rounded mean of the single-light frames --
+ * under the base colour's alpha byte; a pixel without it is its base colour.
+ * With every w_i in {0, 1} that is rt_lights_resolve(base, popcount(mask &
+ * enabled), popcount(enabled)): the rt_renderer_set_lights frame of the
+ * enabled lights.
+ *
+ * rt_relight_capture_start: the validity rules and -2 refusals of
+ * rt_render_aov_start, and -2 without RT_RENDER_SHADOWS (nothing to relight).
+ * An ordinary launch as that one is (no lane, behind the frames in flight on
+ * both lanes), the same launch words and tag.  rt_aov_base.vxbin and
+ * rt_relight.vxbin (the kernel directory's, else the library's) are loaded by
+ * the first call and kept; the record and base-colour buffers are allocated by
+ * the first call after a configure (rt_renderer_configure and
+ * rt_renderer_free release them).
+ *
+ * rt_render_relight_start(r, weights, n): one launch of rt_relight into the
+ * framebuffer in use -- rt_read_framebuffer returns it, rt_render_wait covers
+ * it, rt_render_kernel_ms describes it (it counts nothing: rt_render_stats'
+ * counters are 0) -- with no host wait and no copy: the weights travel in the
+ * launch words.  Launches queue back to back.  -2 (rt_last_error says why)
+ * when there is no capture since the last rt_renderer_configure /
+ * rt_renderer_set_light / rt_renderer_set_lights /
+ * rt_renderer_set_path_lights (those calls end the session: the masks describe
+ * other lights), when n is not the capture's light count, when every weight
+ * is 0.  Frames rendered in between leave records and base colours alone. */
+int rt_relight_capture_start(rt_renderer_h r);
+int rt_relight_capture(rt_renderer_h r);    /* start + wait */
+int rt_render_relight_start(rt_renderer_h r, const uint8_t* weights, uint32_t n);
+int rt_render_relight(rt_renderer_h r, const uint8_t* weights, uint32_t n);  /* start + wait */
+/* the capture's base colours in framebuffer order, count >= the framebuffer's pixels (waits
+ * for the device) */
+int rt_read_relight_base(rt_renderer_h r, uint32_t* out, uint64_t count);
+/* the relit pixel restated on the host, from a pixel's base colour and its record's depth_flags
+ * and light_mask; base_argb when n is outside 1..RT_MAX_LIGHTS or W = 0 */
+uint32_t rt_relight_resolve(uint32_t base_argb, uint32_t depth_flags, uint32_t light_mask, const uint8_t* weights,
+                            uint32_t n);
+
 /* Read back one per-resolution record array of the current configuration
  * (layouts: kernels/rt_common.h; NO REFERENCE).  out NULL = size query
  * (*size = bytes). */

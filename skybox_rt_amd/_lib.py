@@ -31,7 +31,8 @@ REQUIRED = ("libvortex.so", "libvortex-hip.so", "librtapp.so", "rtapp",
             "librt_shard.so", "rt_setup.vxbin", "bvh_sah.vxbin", "om.vxbin", "omapp", "rasterapp",
             "pt_primary.vxbin", "pt_primary_stats.vxbin", "pt_queue.vxbin", "pt_queue_stats.vxbin",
             "rt_om.vxbin", "pt_accum.vxbin", "rt_lights.vxbin", "rt_lights_stats.vxbin",
-            "pt_lights.vxbin", "pt_lights_accum.vxbin", "tex_kat.vxbin", "rt_aov.vxbin")
+            "pt_lights.vxbin", "pt_lights_accum.vxbin", "tex_kat.vxbin", "rt_aov.vxbin",
+            "rt_aov_base.vxbin", "rt_relight.vxbin")
 
 
 class NativeLibraryMissing(RuntimeError):

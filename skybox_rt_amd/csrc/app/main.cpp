@@ -31,7 +31,11 @@
 // lights, written as a 16-byte header ('RTAV', width, height, 16) and the
 // rt_aov_t records in framebuffer order (with -G: this rank's compact tiles),
 // and one line "AOV: <geometry pixels> geometry, <shadow rays> shadow rays,
-// <occluded> occluded"; multi-GPU (one process per GPU over
+// <occluded> occluded"; -W w0,w1,...: with -S, one weight 0..255 per light of
+// -L / -M -- after the frame a relight capture (rt_relight_capture) and one
+// relight launch under the weights (rt_render_relight), whose frame is the one
+// written to -o, and one line "Relight: <n> lights, weights w0,w1,...";
+// multi-GPU (one process per GPU over
 // librt_shard.so / RCCL): -G rank,ranks -I idfile -- this process renders
 // 32x32 tiles t with t % ranks == rank, rank 0 writes the RCCL communicator
 // id to `idfile` (the others wait for it), every frame ends with
@@ -81,6 +85,7 @@ bool om_layers = false;               // -O: RT_SCENE_OM_LAYERS
 uint32_t accum_samples = 0;           // -A: with -P, accumulate this many samples per pixel
 std::vector<std::array<float, 3>> more_lights;  // -M: lights beside the one of -L
 const char* aov_file = nullptr;       // -V: write the frame's visibility records
+const char* weights_arg = nullptr;    // -W: relight the frame under these per-light weights
 
 #ifdef RT_APP_RASTER
 const char* kOpts = "t:i:o:r:w:h:k:n:z?";
@@ -90,7 +95,7 @@ void usage() {
               "[-k tilelogsize] [-n repeat]\n");
 }
 #else
-const char* kOpts = "t:s:e:i:o:r:w:h:k:n:L:M:P:G:I:B:A:V:uxyzSRFHO?";
+const char* kOpts = "t:s:e:i:o:r:w:h:k:n:L:M:P:G:I:B:A:V:W:uxyzSRFHO?";
 void usage() {
   std::printf("Vortex 3D Rendering Test (MI355X).\n"
               "Usage: [-t trace] [-s startdraw] [-e enddraw] [-o output] [-r reference] [-w width] "
@@ -101,6 +106,7 @@ void usage() {
               "       [-A samples: with -P, accumulate that many samples per pixel on the device and "
               "write their mean]\n"
               "       [-V file: the frame's per-pixel visibility records (primary + shadow frames)]\n"
+              "       [-W w0,w1,...: with -S, relight the frame under one weight 0..255 per light of -L / -M]\n"
               "       env RT_KERNEL_DIR: kernel images; RT_ASSETS_PATHS: search directories\n");
 }
 #endif
@@ -149,6 +155,7 @@ int main(int argc, char** argv) {
     case 'O': om_layers = true; break;
     case 'A': accum_samples = (uint32_t)std::atoi(optarg); break;
     case 'V': aov_file = optarg; break;
+    case 'W': weights_arg = optarg; break;
 #endif
     case '?': usage(); return 0;
     default: usage(); return -1;  // -i: in the reference's option string, never handled
@@ -184,6 +191,24 @@ int main(int argc, char** argv) {
   if (accum_samples && (bounces < 0 || rank >= 0)) {
     std::printf("Error: -A samples needs -P bounces (path tracing), one rank\n");
     return 1;
+  }
+  std::vector<uint8_t> weights;
+  if (weights_arg) {
+    bool ok = shadows && rank < 0 && *weights_arg != 0;
+    for (const char* q = weights_arg; ok;) {
+      char* end = nullptr;
+      const long v = std::strtol(q, &end, 10);
+      ok = end != q && v >= 0 && v <= 255 && (*end == ',' || *end == 0);
+      if (ok) weights.push_back((uint8_t)v);
+      if (!ok || *end == 0) break;
+      q = end + 1;
+    }
+    if (!ok || weights.size() != more_lights.size() + 1) {
+      std::printf("Error: -W w0,w1,... needs -S, one rank and one weight in 0..255 per light of -L / -M (%zu)\n",
+                  more_lights.size() + 1);
+      usage();
+      return 1;
+    }
   }
   const bool sharded = rank >= 0;
   if (sharded && (ranks < 1 || rank >= ranks || raster)) {
@@ -354,6 +379,14 @@ int main(int argc, char** argv) {
     }
     std::printf("AOV: %llu geometry, %llu shadow rays, %llu occluded\n", (unsigned long long)as.geometry_hits,
                 (unsigned long long)as.shadow_rays, (unsigned long long)as.occluded);
+  }
+  if (weights_arg) {
+    // the frame relit from its records and base colours: the framebuffer written below
+    RT_CHECK(rt_relight_capture(r));
+    RT_CHECK(rt_render_relight(r, weights.data(), (uint32_t)weights.size()));
+    std::string ws;
+    for (size_t i = 0; i < weights.size(); ++i) ws += (i ? "," : "") + std::to_string(weights[i]);
+    std::printf("Relight: %zu lights, weights %s\n", weights.size(), ws.c_str());
   }
   int errors = 0;
   if (std::strcmp(output_file, "null") != 0 && (!sharded || rank == 0)) {

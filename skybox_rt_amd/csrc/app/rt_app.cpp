@@ -546,6 +546,7 @@ int rt_renderer_set_light(rt_renderer_h r, const float light[3]) {
     return fail("rt_renderer_set_light: the configuration traces no shadow rays");
   uint32_t launches = 0;
   r->nlights = 0;  // back to one light (rt_renderer_set_lights)
+  r->relight_n = 0;  // a capture's masks describe the lights before (rt_relight_capture_start)
   if (rtapp::set_light(r, light, &launches) != 0) return -1;
   r->setup.slist_built = r->sl_mode ? 1u : 0u;
   // a moved light changes what the accumulated samples estimate: the next
@@ -604,6 +605,7 @@ static int set_several_lights(rt_renderer_h r, const float (*lights)[3], uint32_
 int rt_renderer_set_lights(rt_renderer_h r, const float (*lights)[3], uint32_t n) {
   if (!r) return fail("null argument");
   if (!r->configured) return fail("renderer not configured");
+  r->relight_n = 0;  // whatever becomes of the call, a capture's masks are not trusted past it
   if (n < 1 || n > RT_MAX_LIGHTS) return fail("rt_renderer_set_lights: 1 to 16 lights", -2);
   if (!lights) return fail("null argument");
   const uint32_t f = r->params.flags;
@@ -676,6 +678,7 @@ int rt_renderer_set_path_lights(rt_renderer_h r, const float (*lights)[3], uint3
   // whatever becomes of the call, the frames after it are not the ones before: a refusal
   // leaves the single light (as after rt_renderer_set_light), and accumulated samples start over
   r->nlights = 0;
+  r->relight_n = 0;
   if (r->accum_on) {
     r->accum_reset = true;
     r->accum_n = 0;
@@ -1216,6 +1219,14 @@ int rt_renderer_configure(rt_renderer_h r, const rt_render_params_t* p) {
     r->aov = nullptr;
   }
   r->aov_bytes = 0;
+  // and the base colours of a relight capture; the capture itself is over
+  if (r->relight_base) {
+    if (vx_ready_wait(r->dev, VX_MAX_TIMEOUT) != 0) return fail("vx_ready_wait failed");
+    vx_mem_free(r->relight_base);
+    r->relight_base = nullptr;
+  }
+  r->relight_base_bytes = 0;
+  r->relight_n = 0;
   r->nlights = 0;  // a configure returns to one light (rt_renderer_set_lights)
   rt_kernel_arg_t& a = r->arg;
   a.width = p->width;
@@ -1440,8 +1451,9 @@ int rt_renderer_configure(rt_renderer_h r, const rt_render_params_t* p) {
   // (and behind that the background tier's: rt_tier_arg_t, constant until the next configure)
   // (and the light table of rt_renderer_set_lights)
   // (and the visibility records' area: rt_render_aov_start writes it)
+  // (and the relight area: rt_relight_capture_start writes it)
   if (!r->args &&
-      upload(r->dev, nullptr, RT_AOV_ARG_OFFSET + sizeof(rt_aov_arg_t), &r->args, &args_addr))
+      upload(r->dev, nullptr, RT_RELIGHT_ARG_OFFSET + sizeof(rt_relight_arg_t), &r->args, &args_addr))
     return -1;
   if (r->copy_async ? r->copy_async(r->args, &a, 0, sizeof(a)) != 0
                     : vx_copy_to_dev(r->args, &a, 0, sizeof(a)) != 0)
@@ -1683,38 +1695,48 @@ uint32_t rt_accum_resolve(const uint32_t rec[4], uint32_t alpha_argb) {
 
 static_assert(sizeof(rt_aov_t) == 16, "one 16-byte record per pixel");
 
-int rt_render_aov_start(rt_renderer_h r) {
-  if (!r || !r->configured) return fail("renderer not configured");
+// What the record launches share (`who`: rt_render_aov, rt_relight_capture).  The admission checks:
+static int aov_admit(rt_renderer_h r, const std::string& who) {
   const uint32_t f = r->params.flags;
   if (f & (RT_RENDER_PATH | RT_RENDER_FLAT | RT_RENDER_RASTER | RT_RENDER_INSTRUMENTED))
-    return fail("rt_render_aov: a primary+shadow frame only (no RT_RENDER_PATH / FLAT / RASTER / INSTRUMENTED)", -2);
+    return fail(who + ": a primary+shadow frame only (no RT_RENDER_PATH / FLAT / RASTER / INSTRUMENTED)", -2);
   if (!r->sc->tail_prims.empty())
-    return fail("rt_render_aov: a scene with an ordered tail has no visibility records (its tail's fragments are "
+    return fail(who + ": a scene with an ordered tail has no visibility records (its tail's fragments are "
                 "merged, not traced)", -2);
   // (a scene without geometry traces no shadow ray and walks no tree: any image serves it)
   if (r->arg.num_geom > 0 && r->generic_tree())
-    return fail("rt_render_aov: rt_aov walks the binary16 BVH4 only; this tree runs the generic (deep) images", -2);
-  const uint32_t nl = r->nlights >= 2 ? r->nlights : 0u;
-  if (nl != 0 && !r->set_tag) return fail("rt_render_aov: the driver passes no launch tag (several lights)", -2);
-  // the image, by the per-file rule: the kernel directory's file, else the library's
-  if (!r->aov_img &&
-      upload_image(r, rtimg::resolve_file(r->kdir, lib_dir(), "rt_aov.vxbin", file_exists), &r->aov_img))
-    return -1;
+    return fail(who + ": rt_aov walks the binary16 BVH4 only; this tree runs the generic (deep) images", -2);
+  if (r->nlights >= 2 && !r->set_tag) return fail(who + ": the driver passes no launch tag (several lights)", -2);
+  return 0;
+}
+
+// an image outside img[], by the per-file rule: the kernel directory's file, else the library's
+static int aov_image(rt_renderer_h r, const char* file, vx_buffer_h* img) {
+  return !*img && upload_image(r, rtimg::resolve_file(r->kdir, lib_dir(), file, file_exists), img) ? -1 : 0;
+}
+
+// the record buffer of the configuration, allocated by the first launch after a configure
+static int aov_records(rt_renderer_h r) {
   const uint64_t bytes = r->cbuf_bytes * 4;  // 16 B per framebuffer pixel
-  if (!r->aov || r->aov_bytes != bytes) {
-    // (upload frees the old buffer: not under launches still writing it)
-    if (r->aov && vx_ready_wait(r->dev, VX_MAX_TIMEOUT) != 0) return fail("vx_ready_wait failed");
-    uint64_t addr = 0;
-    r->aov_bytes = 0;
-    if (upload(r->dev, nullptr, bytes, &r->aov, &addr)) return -1;
-    r->aov_bytes = bytes;
-    rt_aov_arg_t aa{};
-    aa.aov_addr = addr;
-    // behind the launches in flight (they read the areas in front), ahead of every launch started after it
-    if (r->copy_async ? r->copy_async(r->args, &aa, RT_AOV_ARG_OFFSET, sizeof(aa)) != 0
-                      : vx_copy_to_dev(r->args, &aa, RT_AOV_ARG_OFFSET, sizeof(aa)) != 0)
-      return fail("visibility record argument upload failed");
-  }
+  if (r->aov && r->aov_bytes == bytes) return 0;
+  // (upload frees the old buffer: not under launches still writing it)
+  if (r->aov && vx_ready_wait(r->dev, VX_MAX_TIMEOUT) != 0) return fail("vx_ready_wait failed");
+  uint64_t addr = 0;
+  r->aov_bytes = 0;
+  if (upload(r->dev, nullptr, bytes, &r->aov, &addr)) return -1;
+  r->aov_bytes = bytes;
+  rt_aov_arg_t aa{};
+  aa.aov_addr = addr;
+  // behind the launches in flight (they read the areas in front), ahead of every launch started after it
+  if (r->copy_async ? r->copy_async(r->args, &aa, RT_AOV_ARG_OFFSET, sizeof(aa)) != 0
+                    : vx_copy_to_dev(r->args, &aa, RT_AOV_ARG_OFFSET, sizeof(aa)) != 0)
+    return fail("visibility record argument upload failed");
+  return 0;
+}
+
+// one launch of a record image (rt_aov, rt_aov_base) under the lights in use
+static int aov_launch(rt_renderer_h r, vx_buffer_h img) {
+  const uint32_t nl = r->nlights >= 2 ? r->nlights : 0u;
   // one light: the light (and, while its lists wait for a light that stays, the switch to the BVH
   // walk) in the launch words, as a frame carries them; several: the table, their number the tag
   uint32_t lw[4] = {0, 0, 0, 0};
@@ -1722,14 +1744,22 @@ int rt_render_aov_start(rt_renderer_h r) {
     std::memcpy(lw, r->arg.light, sizeof(r->arg.light));
     lw[3] = RT_LW_LIGHT | (r->sl_stale ? RT_LW_NO_SLIST : 0u);
   }
-  if (r->set_counters && r->set_counters(r->dev, (f & RT_RENDER_COUNTERS) ? 1 : 0) != 0)
+  if (r->set_counters && r->set_counters(r->dev, (r->params.flags & RT_RENDER_COUNTERS) ? 1 : 0) != 0)
     return fail("vx_hip_set_counters failed");
   if (r->set_words && r->set_words(r->dev, lw, 4) != 0) return fail("vx_hip_set_launch_words failed");
   if (nl != 0 && r->set_tag(r->dev, nl) != 0) return fail("vx_hip_set_launch_tag failed");
   // an ordinary launch (no lane asked for) on the image's own grid: the driver orders it behind
   // the frames in flight on both lanes and ahead of what starts after it
-  if (vx_start(r->dev, r->aov_img, r->args) != 0) return fail("vx_start failed");
+  if (vx_start(r->dev, img, r->args) != 0) return fail("vx_start failed");
   return 0;
+}
+
+int rt_render_aov_start(rt_renderer_h r) {
+  if (!r || !r->configured) return fail("renderer not configured");
+  if (const int e = aov_admit(r, "rt_render_aov")) return e;
+  if (aov_image(r, "rt_aov.vxbin", &r->aov_img) != 0) return -1;
+  if (const int e = aov_records(r)) return e;
+  return aov_launch(r, r->aov_img);
 }
 
 int rt_render_aov(rt_renderer_h r) {
@@ -1749,6 +1779,105 @@ int rt_read_aov(rt_renderer_h r, rt_aov_t* out, uint64_t count) {
 uint32_t rt_aov_relight(uint32_t plain_argb, uint32_t light_mask, uint32_t k) {
   if (k < 1 || k > RT_MAX_LIGHTS) return plain_argb;
   return rt_lights_mix(plain_argb, (uint32_t)__builtin_popcount(light_mask & ((1u << k) - 1u)), k);
+}
+
+// ---- relighting from the visibility records (vx_rt.h; NO REFERENCE) --------
+
+int rt_relight_capture_start(rt_renderer_h r) {
+  if (!r || !r->configured) return fail("renderer not configured");
+  if (const int e = aov_admit(r, "rt_relight_capture")) return e;
+  if (!(r->params.flags & RT_RENDER_SHADOWS))
+    return fail("rt_relight_capture: a frame without RT_RENDER_SHADOWS has nothing to relight", -2);
+  if (!r->set_tag || !r->set_words)
+    return fail("rt_relight_capture: the driver passes no launch tag / words (the relight launch's weights)", -2);
+  if (aov_image(r, "rt_aov_base.vxbin", &r->aov_base_img) != 0 ||
+      aov_image(r, "rt_relight.vxbin", &r->relight_img) != 0)
+    return -1;
+  r->relight_n = 0;
+  if (const int e = aov_records(r)) return e;
+  if (!r->relight_base || r->relight_base_bytes != r->cbuf_bytes) {
+    if (r->relight_base && vx_ready_wait(r->dev, VX_MAX_TIMEOUT) != 0) return fail("vx_ready_wait failed");
+    const uint64_t npix = r->cbuf_bytes / 4;
+    // Compact tiles overhanging the image hold pixels no launch writes: the framebuffer keeps
+    // its clear colour there, and so does a relit one -- base colour the clear colour, record 0
+    // (no shadow ray).  Once per configuration, and only where such pixels exist.
+    const bool overhang = (r->arg.flags & RT_FLAG_COMPACT) && ((r->arg.width | r->arg.height) & 31u) != 0;
+    std::vector<uint32_t> fill;
+    if (overhang) {
+      fill.assign(npix * 4, 0u);
+      if (r->aov_bytes && vx_copy_to_dev(r->aov, fill.data(), 0, r->aov_bytes) != 0)
+        return fail("vx_copy_to_dev failed");
+      fill.assign(npix, r->arg.clear_color);
+    }
+    rt_relight_arg_t ra{};
+    r->relight_base_bytes = 0;
+    if (upload(r->dev, overhang ? fill.data() : nullptr, r->cbuf_bytes, &r->relight_base, &ra.base_addr)) return -1;
+    r->relight_base_bytes = r->cbuf_bytes;
+    ra.npix = (uint32_t)npix;
+    ra.cbuf1_off = r->cbuf1_off;
+    if (r->copy_async ? r->copy_async(r->args, &ra, RT_RELIGHT_ARG_OFFSET, sizeof(ra)) != 0
+                      : vx_copy_to_dev(r->args, &ra, RT_RELIGHT_ARG_OFFSET, sizeof(ra)) != 0)
+      return fail("relight argument upload failed");
+  }
+  if (const int e = aov_launch(r, r->aov_base_img)) return e;
+  r->relight_n = r->nlights >= 2 ? r->nlights : 1u;
+  return 0;
+}
+
+int rt_relight_capture(rt_renderer_h r) {
+  const int e = rt_relight_capture_start(r);
+  return e ? e : rt_render_wait(r);
+}
+
+int rt_render_relight_start(rt_renderer_h r, const uint8_t* weights, uint32_t n) {
+  if (!r || !r->configured) return fail("renderer not configured");
+  if (!weights) return fail("null argument");
+  if (r->relight_n == 0)
+    return fail("rt_render_relight: no capture since the last configure / set_light / set_lights / set_path_lights "
+                "(rt_relight_capture)", -2);
+  if (n != r->relight_n)
+    return fail("rt_render_relight: " + std::to_string(n) + " weights for the capture's " +
+                std::to_string(r->relight_n) + " lights", -2);
+  uint32_t lw[4] = {0, 0, 0, 0}, W = 0;
+  std::memcpy(lw, weights, n);
+  for (uint32_t i = 0; i < n; ++i) W += weights[i];
+  if (W == 0) return fail("rt_render_relight: every weight is 0", -2);
+  // into the framebuffer in use, as a frame of rt_render goes: no flip, no lane
+  const int buf = r->cur_buf < 0 ? 0 : r->cur_buf;
+  const uint32_t tag = n | (buf ? RT_RL_TAG_CBUF1 : 0u) | (rt_relight_div(W).m << RT_RL_TAG_M_SHIFT);
+  // (the launch counts nothing: no counter rows)
+  if (r->set_counters && r->set_counters(r->dev, 0) != 0) return fail("vx_hip_set_counters failed");
+  if (r->set_words(r->dev, lw, 4) != 0) return fail("vx_hip_set_launch_words failed");
+  if (r->set_tag(r->dev, tag) != 0) return fail("vx_hip_set_launch_tag failed");
+  if (vx_start(r->dev, r->relight_img, r->args) != 0) return fail("vx_start failed");
+  r->prev_buf = -1;
+  r->cur_buf = buf;
+  return 0;
+}
+
+int rt_render_relight(rt_renderer_h r, const uint8_t* weights, uint32_t n) {
+  const int e = rt_render_relight_start(r, weights, n);
+  return e ? e : rt_render_wait(r);
+}
+
+int rt_read_relight_base(rt_renderer_h r, uint32_t* out, uint64_t count) {
+  if (!r || !out || !r->configured) return fail("renderer not configured");
+  if (!r->relight_base) return fail("rt_read_relight_base: no capture (rt_relight_capture)", -2);
+  if (count * 4 < r->relight_base_bytes) return fail("buffer too small");
+  // (a shard without a tile has no pixel)
+  return (r->relight_base_bytes == 0 || vx_copy_from_dev(out, r->relight_base, 0, r->relight_base_bytes) == 0)
+             ? 0 : fail("vx_copy_from_dev failed");
+}
+
+uint32_t rt_relight_resolve(uint32_t base_argb, uint32_t depth_flags, uint32_t light_mask, const uint8_t* weights,
+                            uint32_t n) {
+  if (!weights || n < 1 || n > RT_MAX_LIGHTS || !(depth_flags & RT_AOV_SHADOW_RAY)) return base_argb;
+  uint32_t w[4] = {0, 0, 0, 0}, W = 0;
+  std::memcpy(w, weights, n);
+  for (uint32_t i = 0; i < n; ++i) W += weights[i];
+  if (W == 0) return base_argb;
+  const rt_relight_div_t d = rt_relight_div(W);
+  return rt_relight_mix(base_argb, rt_relight_occluded(light_mask, w, n), W, d.s, d.m);
 }
 
 int rt_render_stats(rt_renderer_h r, rt_stats_t* st) {

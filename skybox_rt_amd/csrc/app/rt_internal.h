@@ -121,6 +121,15 @@ struct rt_renderer {
   // framebuffer pixel), named in the argument buffer behind the light table
   vx_buffer_h aov_img = nullptr, aov = nullptr;
   uint64_t aov_bytes = 0;
+  // relighting (vx_rt.h rt_relight_capture_start / rt_render_relight_start): the rt_aov_base and
+  // rt_relight images, loaded and kept the same way, and the base-colour buffer of the current
+  // configuration (rt_common.h rt_relight_arg_t: 4 B per framebuffer pixel) beside the records.
+  // relight_n: the lights in use at the last capture, 0 while the records and base colours
+  // describe no lights in use -- before a capture, and after a configure or any call that
+  // changes the lights
+  vx_buffer_h aov_base_img = nullptr, relight_img = nullptr, relight_base = nullptr;
+  uint64_t relight_base_bytes = 0;
+  uint32_t relight_n = 0;
   vx_buffer_h nodes = nullptr, nodes4 = nullptr, tris = nullptr, layers = nullptr, dcs = nullptr, tex = nullptr;
   vx_buffer_h ptris = nullptr, geom = nullptr, oms = nullptr, bbox = nullptr, zbuf = nullptr;
   vx_buffer_h order = nullptr;
@@ -231,7 +240,7 @@ struct rt_renderer {
                            &order, &vnodes, &vtris, &vlayers, &vgeom, &gather_recv, &gather_image, &prims,
                            &cbuf, &cbuf1, &args, &verts, &pdc, &dcz, &layer_list, &geometry_list, &vis,
                            &blist, &bidx, &cdesc, &sidx, &slist, &pathq, &pathq_ctr, &oidx, &olist, &ovtris,
-                           &accum, &aov, &aov_img};
+                           &accum, &aov, &aov_img, &relight_base, &aov_base_img, &relight_img};
     for (auto* b : bufs) {
       if (*b) vx_mem_free(*b);
       *b = nullptr;

@@ -25,10 +25,19 @@
 // Image rt_aov (Makefile): the binary16 BVH4 only (RT_ONLY_BVH4H), built with
 // RT_LIGHTS for rt_trace.h's shadow_ray / occluded_list forms that take the
 // light and its lists as parameters.
+//
+// Image rt_aov_base (RT_AOV_BASE=1; vx_rt.h rt_relight_capture_start): the same
+// launch, the same records, and the pixel shaded without shadows -- shade_wave
+// as rt_kernel calls it, the colour a frame of this configuration without
+// RT_RENDER_SHADOWS stores -- written at the pixel's framebuffer index into the
+// base-colour buffer (rt_common.h rt_relight_arg_t), for rt_relight_kernel.hip.
 #include <hip/hip_runtime.h>
 
 #ifndef RT_BLOCK_THREADS
 #define RT_BLOCK_THREADS 64
+#endif
+#ifndef RT_AOV_BASE
+#define RT_AOV_BASE 0
 #endif
 #define VX_BLOCK_THREADS RT_BLOCK_THREADS  // vx_spawn.h: the workgroup size as a constant
 #include "rt_trace.h"
@@ -47,6 +56,15 @@ __device__ __forceinline__ uint32_t aov_base(const Scene& S) {
   asm volatile("" : "+s"(p));
   return (uint32_t)((const __attribute__((address_space(4))) rt_aov_arg_t*)p)->aov_addr;
 }
+
+#if RT_AOV_BASE
+// the base-colour buffer, the same way
+__device__ __forceinline__ uint32_t base_colours(const Scene& S) {
+  uint64_t p = S.argp + RT_RELIGHT_ARG_OFFSET;
+  asm volatile("" : "+s"(p));
+  return (uint32_t)((const __attribute__((address_space(4))) rt_relight_arg_t*)p)->base_addr;
+}
+#endif
 
 // The winner's depth word after the packet walk of the tree (no block lists),
 // which returns the pid only: the word vis_test computed for it, from the same
@@ -75,7 +93,7 @@ __device__ __forceinline__ bool light_occluded(const Scene& S, const Ray& p, flo
 }
 
 __device__ __forceinline__ void kernel_body(const vx_task_t& task, const Scene& S, uint32_t nl, uint32_t aov,
-                                            Counters& cnt) {
+                                            uint32_t base, Counters& cnt) {
   const uint32_t t = task.blockIdx.x;
   // the chunk's task map in scalar registers (every lane runs the same chunk)
   const uint32_t c = (uint32_t)__builtin_amdgcn_readfirstlane(t) >> 6;
@@ -99,6 +117,11 @@ __device__ __forceinline__ void kernel_body(const vx_task_t& task, const Scene& 
   }
   cnt.hits += hit >= 0;
   const int32_t spid = resolve_layers(S, x, y, in && hit < 0, hit, cnt);
+#if RT_AOV_BASE
+  // the unshadowed pixel (lanes outside the image have spid < 0 and no store)
+  const uint32_t color = shade_wave(S, spid, x, y, S.clear_color, cnt);
+  if (in) S.A.st_u32(base + 4u * out, color);
+#endif
 
   float th = 0.0f;
   uint32_t df = hz | (hit >= 0 ? RT_AOV_GEOM : 0u), mask = 0;
@@ -139,8 +162,13 @@ VX_MAIN(rt_kernel_arg_t, arg, RT_BLOCK_THREADS) {
   // (the tag is a kernel argument: the light count and the buffer stay in scalar registers)
   const uint32_t nl = vx_launch_tag < RT_MAX_LIGHTS ? vx_launch_tag : RT_MAX_LIGHTS;
   const uint32_t aov = aov_base(S);
+#if RT_AOV_BASE
+  const uint32_t base = base_colours(S);
+#else
+  const uint32_t base = 0;
+#endif
   const int rc = vx_spawn_tasks(
-      S.num_tasks, [&](const vx_task_t& task, const Scene* s) { kernel_body(task, *s, nl, aov, cnt); }, &S);
+      S.num_tasks, [&](const vx_task_t& task, const Scene* s) { kernel_body(task, *s, nl, aov, base, cnt); }, &S);
   // a frame's primary rays and hits; the shadow rays of every light, the masks' set bits
   flush(RT_STAT_PRIMARY, cnt.primary);
   flush(RT_STAT_SHADOW, cnt.shadow);

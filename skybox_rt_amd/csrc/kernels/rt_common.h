@@ -319,6 +319,75 @@ static inline uint32_t rt_lights_mix(uint32_t argb, uint32_t occluded, uint32_t 
   }
   return out;
 }
+// Relighting from the visibility records (vx_rt.h rt_relight_capture_start / rt_render_relight_start).
+// The capture launch (rt_aov_kernel.hip RT_AOV_BASE, image rt_aov_base) writes rt_aov's records and,
+// into the base-colour buffer, the pixel shaded without shadows: one ARGB word per framebuffer
+// pixel at the pixel's framebuffer index.  The relight launch (rt_relight_kernel.hip, image
+// rt_relight) streams both into the framebuffer in use.  Their argument area, behind the five
+// above, which stay where they are: written when the buffers are allocated, in stream order,
+// constant until the next configure.
+typedef struct {
+  uint64_t base_addr;   // the base-colour buffer
+  uint32_t npix;        // framebuffer pixels (records, base colours)
+  uint32_t cbuf1_off;   // the second framebuffer past arg.cbuf_addr, mod 2^32 (RT_RL_TAG_CBUF1)
+} rt_relight_arg_t;
+#define RT_RELIGHT_ARG_OFFSET (RT_AOV_ARG_OFFSET + sizeof(rt_aov_arg_t))
+// A relight launch's words are its 16 weight bytes (light i: byte i & 3 of word i >> 2); its tag:
+#define RT_RL_TAG_N_MASK  0x1fu      // bits 0-4: the lights in use at capture time, 1..RT_MAX_LIGHTS
+#define RT_RL_TAG_CBUF1   0x20u      // bit 5: the framebuffer in use is the second one
+#define RT_RL_TAG_M_SHIFT 8          // bits 8-30: the divisor's multiplier (rt_relight_div_t::m)
+// The relit pixel: light i weighs w_i in 0..255, W = sum w_i >= 1 over the n lights, O = the sum
+// over the lights whose mask bit is set.  A pixel with RT_AOV_SHADOW_RAY is, per channel c of the
+// base colour, the weighted rounded mean of the single-light values -- (2 * ((W - O) * c + O *
+// (c >> 1)) + W) / (2 * W) in integer division -- under the base colour's alpha; any other pixel
+// is its base colour.
+// The division, exact for every d = 2 * W <= 8160: with L = ceil(log2 d) <= 13 and s = 13 - L,
+// d' = d << s lies in (2^12, 2^13] and x' = x << s has floor(x' / d') = floor(x / d).  m =
+// ceil(2^34 / d') < 2^22 + 1, e = m * d' - 2^34 in [0, d'): x' * m / 2^34 = x' / d' + x' * e /
+// (d' * 2^34), and the second term stays below 1 / d' -- so the floor is floor(x' / d') -- while
+// x' * e < 2^34.  x <= 2 * 255 * W + W = 255.5 * d, so x' <= 255.5 * d' < 2^21, and e < 2^13.
+// x' * m < 2^44: the product's high word, shifted right by 2.  The kernel and the host
+// (rt_relight_resolve) share this text; m depends on W alone and reaches the kernel in its tag.
+typedef struct {
+  uint32_t s, m;
+} rt_relight_div_t;
+#if defined(__HIPCC__)
+__host__ __device__
+#endif
+static inline uint32_t rt_relight_shift(uint32_t W) {  // s of d = 2 * W, 1 <= W <= 4080
+  uint32_t L = 1;
+  while ((1u << L) < 2u * W) ++L;
+  return 13u - L;
+}
+static inline rt_relight_div_t rt_relight_div(uint32_t W) {  // (the host's: a 64-bit division)
+  rt_relight_div_t v;
+  v.s = rt_relight_shift(W);
+  const uint64_t d = (uint64_t)(2u * W) << v.s;
+  v.m = (uint32_t)((((uint64_t)1 << 34) + d - 1u) / d);
+  return v;
+}
+#if defined(__HIPCC__)
+__host__ __device__
+#endif
+static inline uint32_t rt_relight_mix(uint32_t base, uint32_t O, uint32_t W, uint32_t s, uint32_t m) {
+  uint32_t out = base & 0xff000000u;
+  for (int sh = 0; sh <= 16; sh += 8) {
+    const uint32_t c = (base >> sh) & 0xffu;
+    const uint32_t x = 2u * ((W - O) * c + O * (c >> 1)) + W;
+    out |= (uint32_t)(((uint64_t)(x << s) * m) >> 34) << sh;
+  }
+  return out;
+}
+// O of a record's mask: the weights of the lights in use whose bit is set (bits >= n ignored)
+#if defined(__HIPCC__)
+__host__ __device__
+#endif
+static inline uint32_t rt_relight_occluded(uint32_t mask, const uint32_t w[4], uint32_t n) {
+  uint32_t O = 0;
+  for (uint32_t i = 0; i < RT_MAX_LIGHTS; ++i)
+    O += (i < n && ((mask >> i) & 1u)) ? (w[i >> 2] >> (8u * (i & 3u))) & 0xffu : 0u;
+  return O;
+}
 // A path-traced frame lit by several point lights (pt_kernel.hip PT_LIGHTS, images pt_lights /
 // pt_lights_accum; vx_rt.h rt_renderer_set_path_lights) reads the first count <=
 // RT_MAX_PATH_LIGHTS entries of the same table, every one with lists (slist_on 1).  The cap is

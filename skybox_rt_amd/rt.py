@@ -177,6 +177,11 @@ def lib():
             "rt_render_aov_start": [vp],
             "rt_render_aov": [vp],
             "rt_read_aov": [vp, vp, u64],
+            "rt_relight_capture_start": [vp],
+            "rt_relight_capture": [vp],
+            "rt_render_relight_start": [vp, vp, u32],
+            "rt_render_relight": [vp, vp, u32],
+            "rt_read_relight_base": [vp, vp, u64],
         }
         for name, argtypes in sig.items():
             fn = getattr(h, name)
@@ -190,6 +195,8 @@ def lib():
         h.rt_path_lights_resolve.restype = u32
         h.rt_aov_relight.argtypes = [u32, u32, u32]
         h.rt_aov_relight.restype = u32
+        h.rt_relight_resolve.argtypes = [u32, u32, u32, vp, u32]
+        h.rt_relight_resolve.restype = u32
         h.rt_last_error.restype = C.c_char_p
         h.rt_last_error.argtypes = []
         _h = h
@@ -594,6 +601,47 @@ class Renderer:
         _check(lib().rt_read_aov(self._h, out.ctypes.data, out.size), "rt_read_aov")
         return out
 
+    # relighting from the records (vx_rt.h rt_relight_capture_start; images rt_aov_base, rt_relight)
+    def relight_capture(self, wait: bool = True) -> None:
+        """One launch writing the visibility records of aov() -- the same records,
+        aov_records() returns them -- and every pixel's base colour, the pixel
+        shaded without shadows (relight_base()), under the lights in use.  What
+        relight() needs; set_light(), set_lights(), set_path_lights() and
+        configure() end it."""
+        if wait:
+            _check(lib().rt_relight_capture(self._h), "rt_relight_capture")
+        else:
+            _check(lib().rt_relight_capture_start(self._h), "rt_relight_capture_start")
+
+    def relight(self, weights, wait: bool = True) -> None:
+        """One streaming launch writing into the framebuffer the captured frame
+        under per-light weights 0..255, one per light in use at capture time: per
+        pixel and channel the weighted rounded mean of the single-light frames
+        (weights 0 / 1: the set_lights frame of the lights with a 1).  No tracing,
+        no host wait, no copy; launches queue back to back (wait=False)."""
+        w = np.asarray(weights)
+        if w.ndim != 1 or w.size == 0 or (w < 0).any() or (w > 255).any():
+            raise RtError("rt_render_relight failed: weights are 0..255, one per light")
+        w = np.ascontiguousarray(w, np.uint8)
+        fn = lib().rt_render_relight if wait else lib().rt_render_relight_start
+        _check(fn(self._h, w.ctypes.data, w.size), "rt_render_relight" if wait else "rt_render_relight_start")
+
+    def relight_base(self) -> np.ndarray:
+        """The base colours of the last relight_capture() (waits for the device):
+        uint32 ARGB [H, W], or [local_tiles * 1024] in the compact framebuffer's
+        order for compact / sharded frames."""
+        p = self.params
+        if p is None:
+            raise RtError("rt_read_relight_base failed: renderer not configured")
+        if p.shard_count > 1 or p.flags & RT_RENDER_COMPACT:
+            n = self.stats()["local_tiles"] * TILE * TILE
+            out = np.zeros(max(n, 1), np.uint32)
+            _check(lib().rt_read_relight_base(self._h, out.ctypes.data, n), "rt_read_relight_base")
+            return out[:n]
+        out = np.zeros((p.height, p.width), np.uint32)
+        _check(lib().rt_read_relight_base(self._h, out.ctypes.data, out.size), "rt_read_relight_base")
+        return out
+
     def stats(self) -> dict:
         s = Stats()
         _check(lib().rt_render_stats(self._h, C.byref(s)), "rt_render_stats")
@@ -720,6 +768,31 @@ def aov_relight(plain_argb, light_mask, k: int):
     key = (a.astype(np.uint64) << np.uint64(32)) | m.astype(np.uint64)
     uniq, inv = np.unique(key.reshape(-1), return_inverse=True)
     vals = np.array([fn(int(u >> np.uint64(32)), int(u & np.uint64(0xFFFFFFFF)), int(k)) for u in uniq], np.uint32)
+    return vals[inv.reshape(-1)].reshape(a.shape)
+
+
+def relight_resolve(base_argb, depth_flags, light_mask, weights):
+    """rt_relight_resolve: the relit pixel from its base colour and its visibility
+    record's depth_flags and light_mask under per-light weights 0..255 (n =
+    len(weights)): with RT_AOV_SHADOW_RAY set, per channel (2 * ((W - O) * c + O *
+    (c >> 1)) + W) // (2 * W), W the weights' sum and O the sum over the lights
+    whose mask bit is set, under the base colour's alpha; else the base colour.
+    Scalars give an int; arrays (broadcast against each other) a uint32 array, the
+    library's function applied to every distinct (pixel, flag, mask) triple."""
+    fn = lib().rt_relight_resolve
+    w = np.ascontiguousarray(np.asarray(weights, np.int64).reshape(-1).astype(np.uint8))
+    wp, n = w.ctypes.data, int(w.size)
+    if np.ndim(base_argb) == 0 and np.ndim(depth_flags) == 0 and np.ndim(light_mask) == 0:
+        return int(fn(int(base_argb) & 0xFFFFFFFF, int(depth_flags) & 0xFFFFFFFF, int(light_mask) & 0xFFFFFFFF, wp, n))
+    a, d, m = np.broadcast_arrays(np.asarray(base_argb).astype(np.uint32), np.asarray(depth_flags).astype(np.uint32),
+                                  np.asarray(light_mask).astype(np.uint32))
+    # (of depth_flags only the shadow-ray bit matters: a key of colour, that bit and the mask's low 16 bits)
+    sray = (d & np.uint32(RT_AOV_SHADOW_RAY)) != 0
+    key = (a.astype(np.uint64) << np.uint64(32)) | (sray.astype(np.uint64) << np.uint64(16)) | \
+        (m & np.uint32(0xFFFF)).astype(np.uint64)
+    uniq, inv = np.unique(key.reshape(-1), return_inverse=True)
+    vals = np.array([fn(int(u >> np.uint64(32)), RT_AOV_SHADOW_RAY if (int(u) >> 16) & 1 else 0, int(u) & 0xFFFF, wp, n)
+                     for u in uniq], np.uint32)
     return vals[inv.reshape(-1)].reshape(a.shape)
 
 
