@@ -130,6 +130,11 @@ int rt_scene_export_bvh4(rt_scene_h scene, float* nodes4);
 /* fixed-point shading records (rt_prim_t) at width x height: int32[num_prims][32] */
 int rt_scene_setup_prims(rt_scene_h scene, uint32_t width, uint32_t height, int32_t* out,
                          uint64_t count);
+/* the background-layer table (RT_REC_BGLAYER) of a width x height frame on the host alone: uint32[2] per
+ * 8x8-block chunk from `first_chunk` on, the 32x32 tiles in the order `order` gives (num_tiles entries;
+ * NULL: row-major), 16 chunks a tile; count = records `out` holds, *size = records written */
+int rt_scene_bg_layers(rt_scene_h scene, uint32_t width, uint32_t height, const uint32_t* order,
+                       uint32_t first_chunk, uint32_t* out, uint64_t count, uint64_t* size);
 /* primary-visibility record of every primitive at width x height (the RT
  * kernels' raster-exact primary rays, rt_common.h): uint32[num_prims][3] =
  * covered-pixel rectangle x0 | x1 << 16, y0 | y1 << 16 (inclusive; empty:
@@ -621,6 +626,10 @@ uint32_t rt_relight_resolve(uint32_t base_argb, uint32_t depth_flags, uint32_t l
 #define RT_REC_CDESC_HOST 15u /* the same table restated on the host from the work order and list headers */
 #define RT_REC_OIDX 16u     /* ordered tail: uint32[2] per local 8x8 block: first list entry, count */
 #define RT_REC_OLIST 17u    /* ordered tail: u32 primitive index per entry (+2 padding entries, RT_OLIST_PAD) */
+#define RT_REC_BGLAYER 18u  /* background tier: uint32[2] per chunk from the first background chunk on, in work
+                             * order, as the device setup built it: pid + 1 of the one screen layer covering the
+                             * chunk's 8x8 block (0xffffffff: none, 0: mixed or off the image), its drawcall */
+#define RT_REC_BGLAYER_HOST 19u /* the same table restated on the host from the work order and the layer records */
 int rt_renderer_export_records(rt_renderer_h r, uint32_t which, void* out, uint64_t bytes,
                                uint64_t* size);
 

@@ -546,6 +546,33 @@ int chunk_desc(rt_renderer* r, uint32_t* launches) {
   return 0;
 }
 
+int bg_layers(rt_renderer* r, uint32_t first, uint64_t* addr, uint32_t* launches) {
+  const rt_kernel_arg_t& a = r->arg;
+  *addr = 0;
+  r->bglayer_n = 0;
+  if (a.cdesc_addr == 0 || a.cdesc_first != 0 || first >= r->cdesc_n) return 0;
+  const uint32_t n = r->cdesc_n - first;
+  uint64_t at = 0;
+  if (ensure(r, (uint64_t)n * sizeof(rt_bglayer_t), &r->bglayer, &at)) return -1;
+  rt_setup_arg_t g;
+  base_arg(r, &g);
+  g.status_addr = r->su.status.addr;
+  g.width = a.width;
+  g.height = a.height;
+  g.cdesc_addr = a.cdesc_addr;
+  g.vlayers_addr = a.vlayers_addr;
+  g.prims_addr = a.prims_addr;
+  g.bgl_addr = at;
+  g.bgl_n = n;
+  g.bgl_first = first;
+  Seq q;
+  q.add(RTS_BGLAYER);
+  if (run_seq(r, g, q, launches) != 0) return -1;
+  *addr = at;
+  r->bglayer_n = n;
+  return 0;
+}
+
 int set_light(rt_renderer* r, const float light[3], uint32_t* launches) {
   rt_kernel_arg_t& a = r->arg;
   for (int i = 0; i < 3; ++i) {

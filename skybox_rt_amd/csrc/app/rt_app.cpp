@@ -742,6 +742,11 @@ int rt_renderer_export_records(rt_renderer_h r, uint32_t which, void* out, uint6
     case RT_REC_SLIST: b = a.slist_on ? r->slist : nullptr; n = (r->sl_entries + 1) * sizeof(rt_tri_t); break;
     case RT_REC_CDESC:
     case RT_REC_CDESC_HOST: b = r->cdesc_n ? r->cdesc : nullptr; n = (uint64_t)r->cdesc_n * sizeof(rt_cdesc_t); break;
+    case RT_REC_BGLAYER:
+    case RT_REC_BGLAYER_HOST:
+      b = r->bglayer_n ? r->bglayer : nullptr;
+      n = (uint64_t)r->bglayer_n * sizeof(rt_bglayer_t);
+      break;
     case RT_REC_OIDX: b = a.otail_count ? r->oidx : nullptr; n = (uint64_t)r->local_tiles * 16 * 8; break;
     case RT_REC_OLIST: b = a.otail_count ? r->olist : nullptr; n = (r->olist_entries + RT_OLIST_PAD) * 4; break;
     default: return fail("unknown record array");
@@ -758,6 +763,24 @@ int rt_renderer_export_records(rt_renderer_h r, uint32_t which, void* out, uint6
         a.width, a.tiles_x, a.shard_index, a.shard_count, (a.flags & RT_FLAG_COMPACT) != 0, a.split_tiles,
         r->local_tiles, order.empty() ? nullptr : order.data(), bidx.empty() ? nullptr : bidx.data());
     if (d.size() * sizeof(rt_cdesc_t) != n) return fail("chunk descriptor count mismatch");
+    std::memcpy(out, d.data(), n);
+    if (size) *size = n;
+    return 0;
+  }
+  if (which == RT_REC_BGLAYER_HOST && out) {
+    // the host restatement (app/setup.cpp BgLayers) from the device's work order, layer records and prims
+    if (bytes < n) return fail("buffer too small");
+    std::vector<uint32_t> order(a.order_addr ? r->local_tiles : 0u);
+    std::vector<rt_vtri_t> vl(r->sc->layers.size());
+    std::vector<rt_prim_t> prims(np);
+    if ((!order.empty() && vx_copy_from_dev(order.data(), r->order, 0, order.size() * 4) != 0) ||
+        (!vl.empty() && vx_copy_from_dev(vl.data(), r->vlayers, 0, vl.size() * sizeof(rt_vtri_t)) != 0) ||
+        (!prims.empty() && vx_copy_from_dev(prims.data(), r->prims, 0, np * sizeof(rt_prim_t)) != 0))
+      return fail("vx_copy_from_dev failed");
+    const std::vector<rt_bglayer_t> d =
+        rt::BgLayers(a.width, a.height, a.tiles_x, r->local_tiles, order.empty() ? nullptr : order.data(),
+                     r->cdesc_n - r->bglayer_n, vl.data(), (uint32_t)vl.size(), prims.data(), (uint32_t)np);
+    if (d.size() * sizeof(rt_bglayer_t) != n) return fail("background-layer record count mismatch");
     std::memcpy(out, d.data(), n);
     if (size) *size = n;
     return 0;
@@ -787,6 +810,37 @@ int rt_scene_setup_prims(rt_scene_h s, uint32_t width, uint32_t height, int32_t*
       std::memcpy(out + (size_t)(dc.prim_offset + i) * 32, &p, sizeof(p));
     }
   }
+  return 0;
+}
+
+int rt_scene_bg_layers(rt_scene_h s, uint32_t width, uint32_t height, const uint32_t* order,
+                       uint32_t first_chunk, uint32_t* out, uint64_t count, uint64_t* size) {
+  if (!s || !out || width == 0 || height == 0) return fail("bad argument");
+  const uint32_t tiles_x = (width + 31u) / 32u, tiles = tiles_x * ((height + 31u) / 32u);
+  if (order)
+    for (uint32_t i = 0; i < tiles; ++i)
+      if (order[i] >= tiles) return fail("tile order out of range");
+  std::vector<rt_prim_t> prims(s->scene.prims.size());
+  std::vector<rt::VisPrim> vis(prims.size());
+  for (size_t d = 0; d < s->scene.drawcalls.size(); ++d) {
+    const rt::DrawCall& dc = s->scene.drawcalls[d];
+    for (uint32_t i = 0; i < dc.prim_count; ++i) {
+      const uint32_t g = dc.prim_offset + i;
+      rt_bbox_t bb{0, 0};
+      const bool ok = rt::PrimSetup(s->scene.prims[g], width, height, dc.viewport[4], dc.viewport[5],
+                                    &prims[g]) == rt::kSetupOk &&
+                      rt::PrimBBox(s->scene.prims[g], width, height, &bb) == rt::kSetupOk;
+      prims[g].dc = (uint32_t)d;
+      vis[g] = rt::ComputeVisPrim(prims[g], ok, bb, width, height);
+    }
+  }
+  std::vector<rt_vtri_t> vl;
+  for (int32_t g : s->layers) vl.push_back(rt::MakeVisTri(prims[g], vis[g], g));
+  const std::vector<rt_bglayer_t> d = rt::BgLayers(width, height, tiles_x, tiles, order, first_chunk, vl.data(),
+                                                   (uint32_t)vl.size(), prims.data(), (uint32_t)prims.size());
+  if (count < d.size()) return fail("buffer too small");
+  std::memcpy(out, d.data(), d.size() * sizeof(rt_bglayer_t));
+  if (size) *size = d.size();
   return 0;
 }
 
@@ -1484,6 +1538,18 @@ int rt_renderer_configure(rt_renderer_h r, const rt_render_params_t* p) {
     r->img_shape_known[0] = r->img_shape_known[1] = false;
     rt_tier_arg_t ta{};
     ta.bg_first_chunk = r->bg_ok ? r->bg_first : chunks;
+    // the background chunks' layers (rt_common.h rt_bglayer_t): built here, once the heavy tiles are
+    // known, and read by every frame until the next configure -- nothing about the light is in it
+    // (env RT_BG_LAYERS=0: no table, the tier resolves every chunk's layers itself).  Only for a
+    // configuration whose frames can read it: tiered at all (RT_BG_TIER != 0) and not instrumented
+    // (rt_kernel_stats keeps the layer loop).  A frame under several lights (rt_lights, chosen per
+    // frame by rt_renderer_set_lights after configure) ignores the table it finds.
+    r->bglayer_n = 0;
+    const char* ble = std::getenv("RT_BG_LAYERS");
+    if (r->bg_ok && device && r->bg_mode != 0 && !(p->flags & RT_RENDER_INSTRUMENTED) &&
+        !(ble && std::atoi(ble) == 0) &&
+        rtapp::bg_layers(r, r->bg_first, &ta.bglayer_addr, &launches) != 0)
+      return -1;
     if (r->copy_async ? r->copy_async(r->args, &ta, RT_TIER_ARG_OFFSET, sizeof(ta)) != 0
                       : vx_copy_to_dev(r->args, &ta, RT_TIER_ARG_OFFSET, sizeof(ta)) != 0)
       return fail("render argument upload failed");

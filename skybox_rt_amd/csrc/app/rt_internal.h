@@ -137,6 +137,8 @@ struct rt_renderer {
   vx_buffer_h blist = nullptr, bidx = nullptr;  // per-block candidate lists (rt_bentry_t)
   vx_buffer_h cdesc = nullptr;   // chunk descriptor table (rt_cdesc_t, device_setup.cpp chunk_desc)
   uint32_t cdesc_n = 0;          // its records (0: none in this configuration)
+  vx_buffer_h bglayer = nullptr; // background-layer table (rt_bglayer_t, device_setup.cpp bg_layers)
+  uint32_t bglayer_n = 0;        // its records (0: none: untiered, or env RT_BG_LAYERS=0)
   vx_buffer_h sidx = nullptr, slist = nullptr;  // light-space shadow lists (built for sl_light)
   bool sl_mode = false;     // this configuration's shadow rays use the light-space lists
   bool sl_pending = false;  // lists queued by rt_renderer_set_light, status not read yet
@@ -239,7 +241,7 @@ struct rt_renderer {
     vx_buffer_h* bufs[] = {&nodes, &nodes4, &tris, &layers, &dcs, &tex, &ptris, &geom, &oms, &bbox, &zbuf,
                            &order, &vnodes, &vtris, &vlayers, &vgeom, &gather_recv, &gather_image, &prims,
                            &cbuf, &cbuf1, &args, &verts, &pdc, &dcz, &layer_list, &geometry_list, &vis,
-                           &blist, &bidx, &cdesc, &sidx, &slist, &pathq, &pathq_ctr, &oidx, &olist, &ovtris,
+                           &blist, &bidx, &cdesc, &bglayer, &sidx, &slist, &pathq, &pathq_ctr, &oidx, &olist, &ovtris,
                            &accum, &aov, &aov_img, &relight_base, &aov_base_img, &relight_img};
     for (auto* b : bufs) {
       if (*b) vx_mem_free(*b);
@@ -295,6 +297,10 @@ int device_ingest(rt_renderer* r, bool records);
 // rt_cdesc_t), one more launch of the setup image behind the configure's
 // sequence; called once the tiers are known, when the block lists are in use
 int chunk_desc(rt_renderer* r, uint32_t* launches);
+// the background-layer table (rt_common.h rt_bglayer_t) of the chunks from `first` on, one more
+// launch behind chunk_desc's once the heavy tiles are known; *addr 0 and no records when the
+// configuration has no chunk table over every chunk
+int bg_layers(rt_renderer* r, uint32_t first, uint64_t* addr, uint32_t* launches);
 int device_setup(rt_renderer* r, bool raster, bool order_on, bool lists, bool slists, uint32_t* heavy,
                  uint32_t* launches);
 // rt_renderer_set_light: the new light into the render arguments and, when

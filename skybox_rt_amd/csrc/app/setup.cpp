@@ -271,4 +271,33 @@ std::vector<rt_cdesc_t> ChunkDescs(uint32_t width, uint32_t tiles_x, uint32_t sh
   return out;
 }
 
+std::vector<rt_bglayer_t> BgLayers(uint32_t width, uint32_t height, uint32_t tiles_x, uint32_t local_tiles,
+                                   const uint32_t* order, uint32_t first_chunk, const rt_vtri_t* layers,
+                                   uint32_t num_layers, const rt_prim_t* prims, uint32_t num_prims) {
+  std::vector<rt_bglayer_t> out;
+  for (uint32_t c = first_chunk; c < local_tiles * 16u; ++c) {
+    const uint32_t gt = order ? order[c >> 4] : c >> 4, blk = c & 15u;
+    const uint32_t x0 = (gt % tiles_x) * 32u + (blk & 3u) * 8u, y0 = (gt / tiles_x) * 32u + (blk >> 2) * 8u;
+    rt_bglayer_t d{0u, 0u};
+    if (x0 + 8u <= width && y0 + 8u <= height) {
+      int32_t top[64];
+      for (int32_t& t : top) t = -1;
+      for (uint32_t k = num_layers; k-- > 0;)  // drawing order: the later layer overwrites
+        for (uint32_t p = 0; p < 64u; ++p)
+          if (rt_layer_covers(layers[k].edges, layers[k].rx, layers[k].ry, x0 + (p & 7u), y0 + (p >> 3)))
+            top[p] = layers[k].pid;
+      bool same = true;
+      for (uint32_t p = 1; p < 64u; ++p) same = same && top[p] == top[0];
+      if (same && top[0] < 0) {
+        d.pid1 = RT_BGLAYER_NONE;
+      } else if (same && (uint32_t)top[0] < num_prims) {
+        d.pid1 = (uint32_t)top[0] + 1u;
+        d.dc = prims[top[0]].dc;
+      }
+    }
+    out.push_back(d);
+  }
+  return out;
+}
+
 }  // namespace rt

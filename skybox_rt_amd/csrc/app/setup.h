@@ -52,4 +52,13 @@ std::vector<rt_cdesc_t> ChunkDescs(uint32_t width, uint32_t tiles_x, uint32_t sh
                                    uint32_t shard_count, bool compact, uint32_t pos0,
                                    uint32_t local_tiles, const uint32_t* order, const uint32_t* bidx);
 
+// The background-layer table (rt_common.h rt_bglayer_t) restated on the host (kernels/rt_setup.hip
+// phase_bglayer builds it on the device): record i is chunk first_chunk + i of an unsharded frame's
+// whole-block chunks (work-order position c / 16, block c % 16), up to local_tiles * 16.  The
+// block's pixels are painted with the layer records in drawing order (`layers` is last drawn
+// first, as vlayers; each covering layer overwrites), then compared.  `prims`: rt_prim_t by pid.
+std::vector<rt_bglayer_t> BgLayers(uint32_t width, uint32_t height, uint32_t tiles_x, uint32_t local_tiles,
+                                   const uint32_t* order, uint32_t first_chunk, const rt_vtri_t* layers,
+                                   uint32_t num_layers, const rt_prim_t* prims, uint32_t num_prims);
+
 }  // namespace rt

@@ -263,7 +263,8 @@ typedef struct {
 typedef struct {
   uint32_t bg_first_chunk;  // the first chunk of the work order behind the tiles geometry reaches
                             // (16 * heavy tiles): every chunk from here on has an empty block list
-  uint32_t pad[3];
+  uint32_t pad;
+  uint64_t bglayer_addr;    // rt_bglayer_t per chunk from bg_first_chunk on, in work order (0: no table)
 } rt_tier_arg_t;
 #define RT_TIER_ARG_OFFSET (sizeof(rt_kernel_arg_t) + sizeof(rt_accum_arg_t))
 // The light table of a frame lit by several point lights (rt_kernel.hip RT_LIGHTS, images
@@ -424,6 +425,30 @@ typedef struct {
   uint32_t first;   // the block's candidate list: first entry in blist
   uint32_t count;   // its length (bits 0-15) | the framebuffer words per pixel row << 16
 } rt_cdesc_t;
+// The background-layer table (rt_kernel.hip RT_BG_LAYERS): one record per chunk at or behind
+// rt_tier_arg_t::bg_first_chunk, in work order -- which screen layer covers the chunk's 8x8 block,
+// worked out once per configure by the device setup (rt_setup.hip RTS_BGLAYER) with the rule of
+// rt_trace.h resolve_layers_n (painter order: the first covering record of vlayers wins;
+// rt_layer_covers below) and restated on the host (app/setup.cpp BgLayers).  It depends on the
+// scene, the size and the work order, as the chunk table does -- not on the light.
+typedef struct {
+  uint32_t pid1;  // pid + 1 of the one layer primitive that covers all 64 pixels; RT_BGLAYER_NONE: no layer
+                  // covers any of them (the clear colour); 0: mixed, or a pixel outside the image
+  uint32_t dc;    // that primitive's drawcall index (0 without one)
+} rt_bglayer_t;
+#define RT_BGLAYER_NONE 0xffffffffu
+// a screen layer's record covers pixel (px, py): inside its rectangle (corners packed lo | hi << 16,
+// inclusive) and on the inner side of its three edges (a*x + b*y + c with int32 wrap, >= 0: no top-left
+// rule) -- resolve_layers_n's test per lane, the table's builders' per pixel of a block
+#if defined(__HIPCC__)
+__host__ __device__
+#endif
+static inline int rt_layer_covers(const int32_t e[9], uint32_t rx, uint32_t ry, uint32_t px, uint32_t py) {
+  if (px < (rx & 0xffffu) || px > (rx >> 16) || py < (ry & 0xffffu) || py > (ry >> 16)) return 0;
+  for (int k = 0; k < 3; ++k)
+    if ((int32_t)((uint32_t)e[3 * k] * px + (uint32_t)e[3 * k + 1] * py + (uint32_t)e[3 * k + 2]) < 0) return 0;
+  return 1;
+}
 // the reciprocal rt_kernel_arg_t::tiles_x_magic holds for `tiles_x` tiles per row
 static inline uint32_t rt_tiles_x_magic(uint32_t tiles_x) {
   if (tiles_x <= 1) return 0xffffffffu;

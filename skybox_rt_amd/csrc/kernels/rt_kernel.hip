@@ -49,6 +49,22 @@
 #ifndef RT_BG_TIER
 #define RT_BG_TIER 0
 #endif
+// 1 (RT_KERNEL_DEFS): a background-tier wave of rt_kernel takes its chunk's layer and drawcall
+// from the setup's table (rt_common.h rt_bglayer_t) instead of resolving the layers per lane
+// (RT_BG_TABLE).  The instrumented image keeps the layer loop -- its layer_tests count the
+// records a wave fetched -- and so do the several-lights images, which are not judged on
+// overlapped background chunks and stay byte for byte what they were.
+#ifndef RT_BG_LAYERS
+#define RT_BG_LAYERS 0
+#endif
+#if RT_BG_LAYERS && !RT_BG_TIER
+#error "RT_BG_LAYERS is for the background tier"
+#endif
+#if RT_BG_LAYERS && !defined(RT_INSTRUMENT) && !RT_LIGHTS
+#define RT_BG_TABLE 1
+#else
+#define RT_BG_TABLE 0
+#endif
 #if RT_LIGHTS && (RT_FLAT || RT_PATHQ || RT_BVH_WALK || !RT_ONLY_BVH4H)
 #error "RT_LIGHTS is for the primary+shadow list image on the binary16 BVH4"
 #endif
@@ -501,13 +517,14 @@ __device__ __forceinline__ Scene load_scene_bg(const rt_kernel_arg_t* ga, const 
   return s;
 }
 
-__device__ __forceinline__ uint32_t bg_first_chunk(const rt_kernel_arg_t* ga) {
+__device__ __forceinline__ const __attribute__((address_space(4))) rt_tier_arg_t* tier_arg(
+    const rt_kernel_arg_t* ga) {
   const uint64_t p = (uint64_t)ga + RT_TIER_ARG_OFFSET;
   const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)p);
   const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(p >> 32));
-  return ((const __attribute__((address_space(4))) rt_tier_arg_t*)(((uint64_t)hi << 32) | (uint64_t)lo))
-      ->bg_first_chunk;
+  return (const __attribute__((address_space(4))) rt_tier_arg_t*)(((uint64_t)hi << 32) | (uint64_t)lo);
 }
+__device__ __forceinline__ uint32_t bg_first_chunk(const rt_kernel_arg_t* ga) { return tier_arg(ga)->bg_first_chunk; }
 
 // A background-tier wave: wave (blockIdx.x - tg) * kWaves + its index in the
 // workgroup of the (gridDim.x - tg) * kWaves that share the chunks
@@ -520,17 +537,42 @@ __device__ __forceinline__ void bg_tier(const rt_kernel_arg_t* arg, uint32_t tg,
   uint32_t ran = 0;
   // (the wave's index as a scalar: the chunk loop is a scalar loop, no exec mask kept across it)
   const uint32_t wv = (uint32_t)__builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  for (uint32_t c = bg_first_chunk(arg) + (blockIdx.x - tg) * kWaves + wv; c < nchunks; c += nw) {
+  const uint32_t c0 = bg_first_chunk(arg);
+#if RT_BG_TABLE
+  const uint32_t bgl = (uint32_t)tier_arg(arg)->bglayer_addr;  // 0: no table (env RT_BG_LAYERS=0)
+#endif
+  for (uint32_t c = c0 + (blockIdx.x - tg) * kWaves + wv; c < nchunks; c += nw) {
     const uint32_t ln = threadIdx.x & 63u;
     if (c * VX_CHUNK + ln < S.num_tasks) {
       const uint4 d = S.A.sld_u4(S.cdesc + 16u * (c - S.cdesc_first));
+#if RT_BG_TABLE
+      // the chunk's layer from the table, its load in flight with the descriptor's (both addresses
+      // follow from c): a block under one layer primitive -- all 64 pixels inside the image --
+      // skips the layer loop and hands shade_wave that pid in every lane and its drawcall, so the
+      // primitive's and the drawcall's records load together; a block under no layer shades
+      // nothing and stores the clear colour; entry 0 (mixed, or over the image's edge) runs the
+      // layer loop.  (A shade site of its own here, without shade_wave's ballots: 69 SGPR spills
+      // against 26, and the frame rendered alone 3 % slower -- DESIGN.md 4.1 r18.)
+      uint2 e = make_uint2(0u, 0u);
+      if (bgl != 0) e = S.A.sld<uint2>(bgl + 8u * (c - c0));
+#endif
       const uint32_t x = (d.x & 0xffffu) + (ln & 7u);
       const uint32_t y = (d.x >> 16) + (ln >> 3);
       const uint32_t out = d.y + (ln >> 3) * (d.w >> 16) + (ln & 7u);
       const bool in = x < S.width && y < S.height;
       cnt.primary += in;
+#if RT_BG_TABLE
+      int32_t spid = (int32_t)e.x - 1;  // (RT_BGLAYER_NONE: -2, nothing to shade)
+      uint32_t kdc = e.y;
+      if (e.x == 0) {
+        spid = resolve_layers(S, x, y, in, -1, cnt);
+        kdc = RT_NO_DC;
+      }
+      const uint32_t color = shade_wave(S, spid, x, y, S.clear_color, cnt, kdc);
+#else
       const int32_t spid = resolve_layers(S, x, y, in, -1, cnt);
       const uint32_t color = shade_wave(S, spid, x, y, S.clear_color, cnt);
+#endif
       if (in) store_out(S, out, color);
       ++ran;
     }

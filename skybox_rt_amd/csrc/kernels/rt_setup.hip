@@ -1275,6 +1275,42 @@ __device__ void phase_cdesc(const rt_setup_arg_t* a) {
   }
 }
 
+// The background-layer table (rt_common.h rt_bglayer_t): record i is chunk bgl_first + i of the
+// chunk table -- the layer every lane of rt_kernel's resolve_layers_n would come to at the
+// block's 64 pixels with no geometry winner: per pixel the first record of vlayers that covers
+// it (rt_layer_covers), then whether the 64 agree.  Runs in a launch behind the chunk table's.
+__device__ void phase_bglayer(const rt_setup_arg_t* a) {
+  const rt_cdesc_t* cdesc = vx_ptr<const rt_cdesc_t>(a->cdesc_addr);
+  const rt_vtri_t* vl = vx_ptr<const rt_vtri_t>(a->vlayers_addr);
+  const rt_prim_t* prims = vx_ptr<const rt_prim_t>(a->prims_addr);
+  rt_bglayer_t* out = vx_ptr<rt_bglayer_t>(a->bgl_addr);
+  for (uint32_t i = slice_b() * RTS_BLOCK + threadIdx.x; i < a->bgl_n; i += slice_n() * RTS_BLOCK) {
+    const uint32_t o = cdesc[a->bgl_first + i].origin, x0 = o & 0xffffu, y0 = o >> 16;
+    rt_bglayer_t d;
+    d.pid1 = 0;
+    d.dc = 0;
+    if (x0 + 8u <= a->width && y0 + 8u <= a->height) {
+      int32_t pid = -2;  // -2: no pixel yet, -1: no layer, -3: mixed
+      for (uint32_t p = 0; p < 64u && pid != -3; ++p) {
+        int32_t mine = -1;
+        for (uint32_t k = 0; k < a->num_layers; ++k)
+          if (rt_layer_covers(vl[k].edges, vl[k].rx, vl[k].ry, x0 + (p & 7u), y0 + (p >> 3))) {
+            mine = vl[k].pid;
+            break;
+          }
+        pid = pid == -2 || pid == mine ? mine : -3;
+      }
+      if (pid == -1) {
+        d.pid1 = RT_BGLAYER_NONE;
+      } else if (pid >= 0 && (uint32_t)pid < a->num_prims) {
+        d.pid1 = (uint32_t)pid + 1u;
+        d.dc = prims[pid].dc;
+      }
+    }
+    out[i] = d;
+  }
+}
+
 // one wide sub-phase (on this workgroup's slice, slice_b() / slice_n())
 __device__ void run_phase(const rt_setup_arg_t* arg, uint32_t bit) {
   switch (bit) {
@@ -1301,18 +1337,19 @@ __device__ void run_phase(const rt_setup_arg_t* arg, uint32_t bit) {
     case RTS_SFILL: phase_sfill(arg); break;
     case RTS_SSORT: phase_ssort(arg); break;
     case RTS_CDESC: phase_cdesc(arg); break;
+    case RTS_BGLAYER: phase_bglayer(arg); break;
     default: break;
   }
 }
 // the wide sub-phases in run order, with their shares of a partitioned
 // launch's workgroups (the per-primitive scan of PRIMVIS and the per-entry
 // list phases carry the longest per-workgroup chains)
-__constant__ const uint32_t kWide[23][2] = {
+__constant__ const uint32_t kWide[24][2] = {
     {RTS_FILL, 2},   {RTS_PRIMVIS, 16}, {RTS_SPROJ, 3},  {RTS_VTRIS, 1},  {RTS_WEIGHT, 1},  {RTS_LINK, 3},
     {RTS_ROWSUM, 1}, {RTS_CLIMB, 3},   {RTS_COLSUM, 1}, {RTS_HIST, 1},   {RTS_SCATTER, 2}, {RTS_RECORDS, 2},
     {RTS_BCOUNT, 2}, {RTS_BSUM, 1},    {RTS_BOFF, 1},   {RTS_BFILL, 2},  {RTS_BSORT, 4},   {RTS_SCOUNT, 3},
     {RTS_SSUM, 1},   {RTS_SOFF, 2},    {RTS_SFILL, 3},  {RTS_SSORT, 3},
-    {RTS_CDESC, 1}};
+    {RTS_CDESC, 1},  {RTS_BGLAYER, 1}};
 // the wide sub-phases of `ph` (each independent of the others in the same
 // launch).  part: each on its own slice of the grid, in proportion to its
 // share, so they run side by side (a launch then takes about its longest
@@ -1320,11 +1357,11 @@ __constant__ const uint32_t kWide[23][2] = {
 __device__ void run_phases(const rt_setup_arg_t* arg, uint32_t ph, bool part) {
   if ((ph & RTS_CLIMB) && arg->num_nodes <= RTS_CLIMB_WG_NODES) ph &= ~RTS_CLIMB;  // one workgroup: run_scans
   uint32_t total = 0;
-  for (int i = 0; i < 23; ++i) total += (ph & kWide[i][0]) ? kWide[i][1] : 0u;
+  for (int i = 0; i < 24; ++i) total += (ph & kWide[i][0]) ? kWide[i][1] : 0u;
   if (total == 0) return;
   const uint32_t G = gridDim.x;
   uint32_t cum = 0;
-  for (int i = 0; i < 23; ++i) {
+  for (int i = 0; i < 24; ++i) {
     const uint32_t bit = kWide[i][0];
     if (!(ph & bit)) continue;
     uint32_t b0 = 0, b1 = G;

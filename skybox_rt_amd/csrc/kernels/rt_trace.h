@@ -1289,8 +1289,13 @@ __device__ __forceinline__ uint32_t shade_lane(const Scene& S, int32_t pid, uint
 #else
 #define RT_SHADE gfx::shade
 #endif
+// (kdc: the drawcall of a wave's one primitive where the caller knows it -- rt_kernel.hip's
+// background tier, from the setup's table -- so the drawcall record's load does not wait for the
+// primitive's; RT_NO_DC: read it from the primitive record)
+#define RT_NO_DC 0xffffffffu
 __device__ __forceinline__ uint32_t shade_wave(const Scene& S, int32_t spid, uint32_t x,
-                                               uint32_t y, uint32_t color, Counters& cnt) {
+                                               uint32_t y, uint32_t color, Counters& cnt,
+                                               uint32_t kdc = RT_NO_DC) {
   const uint64_t need = __ballot(spid >= 0);
   if (need == 0) return color;
   const bool mine = (need & (1ull << lane_id())) != 0;
@@ -1298,8 +1303,14 @@ __device__ __forceinline__ uint32_t shade_wave(const Scene& S, int32_t spid, uin
   if (__ballot(mine && spid == p0) == need) {
     if (mine) {
       gfx::Prim p;
-      gfx::load_prim<true>(S.A, S.prims + 128u * (uint32_t)p0, p);
-      const gfx::DcState s = gfx::load_dcstate<true>(S.A, S.dcs + 64u * p.dc());
+      gfx::DcState s;
+      if (kdc != RT_NO_DC) {  // both records' loads in flight together
+        gfx::load_prim<true>(S.A, S.prims + 128u * (uint32_t)p0, p);
+        s = gfx::load_dcstate<true>(S.A, S.dcs + 64u * kdc);
+      } else {
+        gfx::load_prim<true>(S.A, S.prims + 128u * (uint32_t)p0, p);
+        s = gfx::load_dcstate<true>(S.A, S.dcs + 64u * p.dc());
+      }
 #ifdef RT_INSTRUMENT
       ++cnt.shaded;
       if (s.flags & RT_DC_TEX) cnt.texel_bytes += (s.filter == VX_TEX_FILTER_BILINEAR ? 4u : 1u) * s.stride;

@@ -72,6 +72,8 @@
 #define RTS_SSCAN    0x1000000u // BSCAN over the cells
 #define RTS_SOFF     0x2000000u // BOFF over the cells -> sidx
 #define RTS_CDESC    0x4000000u // thread per whole-block chunk: rt_cdesc_t (rt_common.h) from order + bidx
+#define RTS_BGLAYER  0x8000000u // thread per background chunk: rt_bglayer_t (rt_common.h) from cdesc + vlayers,
+                                // in a launch of its own once the heavy tiles are known
 
 // status words (u32 [RTS_STATUS_WORDS]): [0] malformed-input flags
 // (RTS_ERR_*), [1] the longest block list, [2] block-list entries in total,
@@ -168,4 +170,8 @@ typedef struct {
   uint64_t cdesc_addr;     // rt_cdesc_t [cdesc_n]
   uint32_t cdesc_pos0;     // the tier's first position in the work order (= the split tiles)
   uint32_t cdesc_compact;  // the framebuffer is the compact shard layout (RT_FLAG_COMPACT)
+  // RTS_BGLAYER: the background-layer table (reads cdesc_addr, vlayers_addr, num_layers, prims_addr)
+  uint32_t bgl_n;          // records: the chunks from bgl_first on
+  uint32_t bgl_first;      // the first background chunk, as an index into the chunk table
+  uint64_t bgl_addr;       // rt_bglayer_t [bgl_n]
 } rt_setup_arg_t;

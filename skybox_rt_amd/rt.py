@@ -38,7 +38,8 @@ RECORDS = {"prims": (0, np.int32, 32), "bbox": (1, np.uint32, 2), "vis": (2, np.
            "geom": (9, np.float32, 12), "bidx": (10, np.uint32, 2), "blist": (11, np.uint32, 4),
            "cdesc": (14, np.uint32, 4), "cdesc_host": (15, np.uint32, 4),
            "sidx": (12, np.uint32, 2), "slist": (13, np.float32, 12),
-           "oidx": (16, np.uint32, 2), "olist": (17, np.uint32, 1)}
+           "oidx": (16, np.uint32, 2), "olist": (17, np.uint32, 1),
+           "bglayer": (18, np.uint32, 2), "bglayer_host": (19, np.uint32, 2)}
 RT_BVH_STACK4_UNUSED = 0xFFFFFFFF
 RT_BVH_BUILD_HOST = 2
 CLEAR_COLOR = 0xFF000000               # draw3d/main.cpp:47
@@ -154,6 +155,7 @@ def lib():
             "rt_launch_rows": [vp, vp, u64, C.POINTER(u64)],
             "rt_scene_setup_prims": [vp, u32, u32, vp, u64],
             "rt_scene_setup_vis": [vp, u32, u32, vp, u64],
+            "rt_scene_bg_layers": [vp, u32, u32, vp, u32, vp, u64, C.POINTER(u64)],
             "rt_scene_vis_tree": [vp, u32, u32, C.c_float, vp, C.POINTER(u32), vp, C.POINTER(u32),
                                   C.POINTER(u32)],
             "rt_framebuffer_device": [vp, C.POINTER(vp), C.POINTER(u64)],
@@ -280,6 +282,21 @@ class Scene:
         _check(lib().rt_scene_setup_prims(self._h, width, height, out.ctypes.data, n),
                "rt_scene_setup_prims")
         return out[:n]
+
+    def bg_layers(self, width: int, height: int, order=None, first_chunk: int = 0) -> np.ndarray:
+        """The background-layer table (uint32[chunks - first_chunk, 2]: pid + 1 of the one
+        screen layer over the chunk's 8x8 block -- 0xffffffff none, 0 mixed or off the image --
+        and its drawcall) of a width x height frame, computed on the host; `order`: the 32x32
+        tiles' work order (default row-major), 16 chunks a tile."""
+        tiles = ((width + 31) // 32) * ((height + 31) // 32)
+        o = None if order is None else np.ascontiguousarray(order, np.uint32)
+        assert o is None or o.size == tiles
+        out = np.zeros((tiles * 16, 2), np.uint32)
+        n = C.c_uint64()
+        _check(lib().rt_scene_bg_layers(self._h, width, height, None if o is None else o.ctypes.data,
+                                        first_chunk, out.ctypes.data, tiles * 16, C.byref(n)),
+               "rt_scene_bg_layers")
+        return out[:n.value]
 
     def setup_vis(self, width: int, height: int) -> np.ndarray:
         """Primary-visibility records (uint32[P, 3]: covered-pixel rectangle
