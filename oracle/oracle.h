@@ -13,8 +13,9 @@
  *     data into tests/golden/).  The reference itself cannot be built here
  *     (cocogfx/softfloat/ramulator submodules are empty, no RISC-V toolchain).
  *   - ray-tracing path (MT visibility, shadow, bounce): NO REFERENCE EXISTS
- *      -> "parity unpinned" beyond primary visibility,
- *     which is cross-checked against the pinned raster path.
+ *     (SURVEY.md section 0.1).  Primary visibility is cross-checked against
+ *     the pinned raster path; shadow rays and the path tracer are held to an
+ *     independent float64 model (tests/rt_reference.py).
  *
  * Numerics: compiled with -ffp-contract=off; every fused multiply-add is an
  * explicit fmaf() so the HIP kernel (which uses the same explicit fmaf()s)

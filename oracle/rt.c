@@ -4,10 +4,12 @@
  * layers, raster-parity shading of the hit, any-hit shadow rays.
  * TEST INFRASTRUCTURE ONLY (see oracle.h).
  *
- * There is NO reference implementation of this path:
- * parity of the RT-specific parts is unpinned; primary visibility is
- * cross-checked against the raster restatement (raster.c), which is pinned by
- * the reference's golden images.  Anchors used:
+ * There is NO reference implementation of this path.
+ * Primary visibility is cross-checked against the raster restatement
+ * (raster.c), which is pinned by the reference's golden images; shadow
+ * verdicts, the plane t and the path tracer are held to an independent
+ * float64 model (tests/rt_reference.py, tests/test_rt_model_cpu.py;
+ * DESIGN.md section 5).  Anchors used:
  *   - pixel centres / framebuffer orientation: gfxutil.cpp:150-152,164-166,211-214 and
  *     draw3d/main.cpp:385-386 (row 0 = NDC y = -1);
  *   - MT == homogeneous edge functions for eye rays: gfxutil.cpp:35-75;
@@ -691,7 +693,11 @@ static uint32_t shade_at(const rt_ctx_t* c, int g, uint32_t x, uint32_t y, orc_r
 /* ---- diffuse path trace -------------------
  * NO REFERENCE: the reference has no lights, normals or materials.  The
  * estimator is the build's own documented choice (DESIGN.md "Path tracing"),
- * restated here op for op as the HIP kernel (kernels/pt_kernel.hip) runs it:
+ * restated here op for op as the HIP kernel (kernels/pt_kernel.hip) runs it
+ * and held to the float64 model of tests/rt_reference.py -- exactly where no
+ * random number reaches a frame, in distribution elsewhere; the PCG stream,
+ * the fall-back after ORC_PT_TRIES and the rounding order are pinned by the
+ * kernels' agreement with this file alone:
  * at every path vertex one shadow ray to the point light (direct term
  * T * max(0, cos)), then -- for `bounces` segments -- a cosine-weighted bounce
  * about the geometric normal; an escaped ray adds T * ORC_PT_SKY; a bounce hit

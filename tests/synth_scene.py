@@ -57,6 +57,65 @@ def make_chain_scene(path: str, n: int, ratio: float = 1.6, base: float = 1e-3) 
     return _write(path, verts, np.full((n, 3), 0.5))
 
 
+# ---- scenes for the RT model (tests/rt_reference.py) ------------------------
+# One flat colour per triangle, no texture: the plain frame shows a triangle
+# in floor(c * 255) per channel, which the model takes as its albedo.
+
+def make_interreflection_scene(path: str) -> str:
+    """48 large overlapping triangles (corners up to 8 apart in w), so that
+    bounce rays hit often: ~330 path pixels at 32x32, mean radiance ~45/255"""
+    return make_scene(path, n=48, seed=5, size=0.35, spread=0.6, w_jitter=8.0)
+
+
+def _tris_to_verts(tris):
+    """[(corner, corner, corner)] of clip (x, y, w) -> _write's verts; depth
+    z / w = 1 - 50 / w grows with w, so the raster's winner is the nearest"""
+    t = np.asarray(tris, np.float64)
+    return [(t[:, k, 0], t[:, k, 1], t[:, k, 2] - 50.0, t[:, k, 2]) for k in range(3)]
+
+
+def _quad(a, b, c, d):
+    return [(a, b, c), (a, c, d)]
+
+
+def make_convex_scene(path: str) -> str:
+    """One tilted quad (two triangles sharing the diagonal) facing the default
+    light and nothing else: no bounce ray can hit, no shadow segment is
+    blocked, so a path frame is alb0 * (cos + 0.25) whatever the seed."""
+    w = lambda x, y: 100.0 + 0.08 * x + 0.05 * y
+    p = [(x, y, w(x, y)) for x, y in ((-60.0, -50.0), (60.0, -50.0), (60.0, 50.0), (-60.0, 50.0))]
+    tris = _quad(*p)
+    return _write(path, _tris_to_verts(tris), np.tile([[0.8, 0.6, 0.4]], (2, 1)))
+
+
+SHADOW_EDGE_LIGHTS = [(10.0, 30.0, 85.0),        # close to the geometry
+                      (0.0, 60.0, 80.0),         # the default light
+                      (-150.0, 400.0, -200.0)]   # far away, behind the eye
+
+
+def make_shadow_edge_scene(path: str) -> str:
+    """A tilted wall behind occluders whose silhouettes cross many pixels: a
+    sliver, a quad of two triangles sharing an edge (a ray through the seam must
+    hit), a comb of narrow spikes; a large triangle beyond the close light (on
+    the line wall -> light past the light: it must not shadow, off screen); a
+    large triangle behind the wall (met by the segment's line before its
+    start); a quad whose eye side faces away from the two near lights (its own
+    plane lies between its pixels' origins and the light)."""
+    ww = lambda x, y: 110.0 + 0.05 * x - 0.03 * y
+    wall = [(x, y, ww(x, y)) for x, y in ((-100.0, -100.0), (100.0, -100.0), (100.0, 100.0), (-100.0, 100.0))]
+    tris = _quad(*wall)
+    tris.append(((-60.0, -40.0, 100.0), (60.0, 30.0, 98.0), (58.0, 36.0, 99.0)))          # sliver
+    ws = lambda x: 97.0 + 0.1 * x
+    tris += _quad((-30.0, 10.0, ws(-30.0)), (0.0, 10.0, ws(0.0)), (0.0, 40.0, ws(0.0)), (-30.0, 40.0, ws(-30.0)))
+    for k in range(6):                                                                     # comb
+        tris.append(((20.0 + 8 * k, -60.0, 101.0), (19.0 + 8 * k, -10.0, 99.0), (16.0 + 8 * k, -10.0, 99.0)))
+    tris.append(((-200.0, 70.0, 60.0), (250.0, 70.0, 60.0), (0.0, 400.0, 58.0)))          # beyond the light
+    tris.append(((-150.0, -150.0, 130.0), (150.0, -150.0, 130.0), (0.0, 200.0, 130.0)))   # behind the wall
+    tris += _quad((-50.0, -45.0, 88.0), (50.0, -45.0, 88.0), (50.0, -75.0, 106.0), (-50.0, -75.0, 106.0))
+    col = np.random.default_rng(11).uniform(0.3, 1.0, (len(tris), 3))
+    return _write(path, _tris_to_verts(tris), col)
+
+
 def _geometry_xml(verts, col, alpha: float = 1.0) -> str:
     """the <vertices> and <primitives> elements of one drawcall"""
     n = len(col)

@@ -8,8 +8,8 @@ samples; the frame is alpha | mean(R) << 16 | mean(G) << 8 | mean(B) with
 mean(c) = (2 * sum_c + n) // (2 * n) and sample 0's alpha.  Records and frames
 must equal it exactly however the samples are split over launches, after
 resets and light changes, with counters, shards, the BVH walk and plain frames
-in between.  No reference exists for this row (parity unpinned beyond the
-oracle)."""
+in between.  No reference exists for this row; the oracle's frames
+themselves are held to the model of tests/rt_reference.py."""
 import os
 import subprocess
 

@@ -7,7 +7,8 @@ frame is, per pixel and colour channel, the rounded mean (2 * sum + K) //
 (2 * K) of the K single-light RT_RENDER_SHADOWS frames, under the primary
 colour's alpha (the same in every one of them); its shadow-ray counters are the
 no-shadow frame's plus every light's own share.  No reference exists for this
-row (parity unpinned beyond the oracle)."""
+row; the oracle's verdicts themselves are held to the model of
+tests/rt_reference.py."""
 import os
 import subprocess
 

@@ -10,8 +10,8 @@ accumulation under K lights is that frame for seed (s0 + j) mod 2^32; a record
 is {sum R, sum G, sum B, n} over the samples' 8-bit values and the accumulated
 frame their rounded mean.  primary_rays, geometry_hits and bounce_rays are one
 single-light frame's, shadow_rays and occluded the sums over the lights (and,
-with bounce_rays, over a launch's samples).  No reference exists for this row
-(parity unpinned beyond the oracle)."""
+with bounce_rays, over a launch's samples).  No reference exists for this row;
+the oracle's frames themselves are held to the model of tests/rt_reference.py."""
 import os
 import subprocess
 

@@ -1,7 +1,9 @@
 """GPU parity tests of the path tracer (pt_kernel.hip; SURVEY.md 8(a) row A7,
 BASELINE config 4) through the C-ABI against the oracle's restatement
 (oracle/rt.c path_trace): framebuffers and ray counters bit-exact.  No
-reference exists for this row (parity unpinned beyond the oracle)."""
+reference exists for this row; the oracle and the device are each held to an
+independent float64 model of the estimator in tests/test_rt_model_cpu.py and
+tests/test_gpu_rt_model.py."""
 import numpy as np
 import pytest
 

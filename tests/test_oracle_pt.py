@@ -1,6 +1,7 @@
 """CPU tests of the path-trace oracle (BASELINE
 config 4).  No reference implementation exists for this row (SURVEY.md
-section 0.1: parity unpinned); these tests pin the oracle's own invariants:
+section 0.1); what it computes is held to an independent float64 model in
+tests/test_rt_model_cpu.py, and these tests pin the oracle's own invariants:
 BVH traversal == brute force, thread-count invariance, agreement with the
 primary+shadow render wherever no path starts, the bounce/shadow ray
 bookkeeping, and a committed digest of its output (tests/golden/pt/, made by
