@@ -6,8 +6,12 @@ instrumented with marker lines, each shipped image's compile line is run
 through the device preprocessor (hipcc -E --cuda-device-only), and a chain
 that takes the same branch in every image that reaches it is replaced by that
 branch.  Chains that differ between images (RT_INSTRUMENT, RT_STAMPS, the
-deep / flat / compact images) stay.  The caller then checks that the shipped
-images rebuild bit-identical.
+deep / compact images) stay.  The images and their defines are the Makefile's
+own: the --genco lines of `make -n -B all`; the sources are the ones those
+lines name, plus rt_trace.h.  A chain reported resolvable is listed with its
+line: an #ifndef default guard or an #error is there to stay.  The caller
+then checks that the shipped images rebuild identical
+(scripts/image_identity.py).
 
     python scripts/prune_knobs.py            # dry run: report
     python scripts/prune_knobs.py --write    # rewrite the sources
@@ -25,32 +29,19 @@ import tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "skybox_rt_amd", "csrc")
 KDIR = os.path.join(CSRC, "kernels")
-FILES = ["rt_trace.h", "rt_kernel.hip", "pt_kernel.hip"]
 
-# the shipped images' defines (skybox_rt_amd/csrc/Makefile: IMAGES and diag)
-RT_BASE = "-DRT_ONLY_BVH4H=1"
-RT_DEFS = RT_BASE + " -DRT_BLOCK_THREADS=128"
-BVH_DEFS = RT_BASE + " -DRT_BLOCK_THREADS=256 -DRT_BVH_WALK=1"
-PT_DEFS = "-DRT_ONLY_BVH4H=1 -DRT_PUSH_UNCOND=1 -DRT_LAZY_TASK_ARGS=0 -DVX_ROWS_GATE=0"
-FLAT_DEFS = "-DRT_FLAT=1 -DRT_BLOCK_THREADS=512"
-# (source, defines) of every shipped image and the diagnostic stamp images
-CONFIGS = []
-for inst in ("", " -DRT_INSTRUMENT"):
-    CONFIGS += [
-        ("rt_kernel.hip", RT_DEFS + inst),
-        ("rt_kernel.hip", BVH_DEFS + inst),
-        ("rt_kernel.hip", "-DRT_MAX_STACK=32" + inst),
-        ("rt_kernel.hip", FLAT_DEFS + inst),
-        ("rt_kernel.hip", RT_DEFS + " -DRT_PATHQ=1" + inst),
-        ("rt_kernel.hip", RT_BASE + " -DRT_BLOCK_THREADS=64 -DRT_STAMPS" + inst),
-        ("rt_kernel.hip", RT_BASE + " -DRT_BLOCK_THREADS=64 -DRT_BVH_WALK=1 -DRT_STAMPS" + inst),
-        ("rt_kernel.hip", FLAT_DEFS + " -DRT_STAMPS" + inst),
-        ("pt_kernel.hip", PT_DEFS + inst),
-        ("pt_kernel.hip", "-DRT_MAX_STACK=32" + inst),
-        ("pt_kernel.hip", "-DPT_MODE=0" + inst),
-        ("pt_kernel.hip", PT_DEFS + " -DPT_MODE=2 -DPT_PAIR=0" + inst),
-        ("pt_kernel.hip", PT_DEFS + " -DRT_STAMPS -DRT_TRACE_CYCLES" + inst),
-    ]
+
+def shipped_configs():
+    """[(source, [defines])] of every kernel image `make all` builds (the shipped images and the
+    diagnostic stamp images): the --genco lines of the Makefile's own dry run"""
+    out = subprocess.run(["make", "-n", "-B", "-C", CSRC, "all"], capture_output=True, text=True, check=True).stdout
+    configs = []
+    for line in out.replace("\\\n", " ").splitlines():
+        words = line.split()
+        if "--genco" in words:
+            configs.append((os.path.basename(words[-1]), [w for w in words if w[:2] in ("-D", "-U")]))
+    return configs
+
 
 DIRECTIVE = re.compile(r"^\s*#\s*(if|ifdef|ifndef|elif|else|endif)\b")
 
@@ -115,25 +106,27 @@ def main():
     tmp = tempfile.mkdtemp(prefix="prune_")
     tk = os.path.join(tmp, "kernels")
     shutil.copytree(KDIR, tk)
-    src = {f: open(os.path.join(KDIR, f)).readlines() for f in FILES}
+    configs = shipped_configs()
+    files = sorted({source for source, _ in configs}) + ["rt_trace.h"]
+    src = {f: open(os.path.join(KDIR, f)).readlines() for f in files}
     chains = {}
-    for f in FILES:
+    for f in files:
         tag = re.sub(r"\W", "_", f)
         inst, chains[f] = instrument(src[f], tag)
         with open(os.path.join(tk, f), "w") as fh:
             fh.writelines(inst)
     seen = []
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    for source, defs in CONFIGS:
+    for source, defs in configs:
         cmd = [hipcc, "-E", "--cuda-device-only", "--offload-arch=gfx950", "-std=c++17",
                "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(CSRC, "runtime"),
-               "-I" + os.path.join(CSRC, "app"), "-I" + tk] + defs.split() + [os.path.join(tk, source)]
+               "-I" + os.path.join(CSRC, "app"), "-I" + tk] + defs + [os.path.join(tk, source)]
         out = subprocess.run(cmd, capture_output=True, text=True)
         if out.returncode != 0:
             sys.exit(out.stderr)
         seen.append(set(re.findall(r"PRUNEMARK_\w+", out.stdout)))
     total_kept = 0
-    for f in FILES:
+    for f in files:
         tag = re.sub(r"\W", "_", f)
         lines = src[f]
         drop = set()      # physical lines to delete
@@ -150,6 +143,8 @@ def main():
                 continue
             keep = taken.pop()
             resolved += 1
+            print(f"  {f}:{ch['branches'][0][0] + 1}: {lines[ch['branches'][0][0]].strip()}  -> "
+                  + (f"branch {keep}" if keep >= 0 else "no branch"))
             for bi, (d, b0, b1) in enumerate(ch["branches"]):
                 # the directive line(s)
                 nxt = ch["branches"][bi + 1][0] if bi + 1 < len(ch["branches"]) else ch["end"]
@@ -161,7 +156,7 @@ def main():
             drop.add(ch["end"])
         kept = len(chains[f]) - resolved
         total_kept += kept
-        print(f"{f}: {len(chains[f])} chains, {resolved} resolved, {kept} kept")
+        print(f"{f}: {len(chains[f])} chains, {resolved} resolvable, {kept} kept")
         if args.write:
             with open(os.path.join(KDIR, f), "w") as fh:
                 fh.writelines(ln for i, ln in enumerate(lines) if i not in drop)

@@ -184,8 +184,7 @@ int run_seq(rt_renderer* r, rt_setup_arg_t& g, const Seq& q, uint32_t* launches)
   g.part = (pe && std::atoi(pe) == 0) ? 0u : 1u;
   for (uint32_t i = 0; i < RTS_MAX_SEQ; ++i) g.seq_phases[i] = i < x.n ? x.ph[i] : 0u;
   if (ensure(r, sizeof(g), &r->su.args) != 0) return -1;
-  const int rc = r->copy_async ? r->copy_async(r->su.args.h, &g, 0, sizeof(g))
-                               : vx_copy_to_dev(r->su.args.h, &g, 0, sizeof(g));
+  const int rc = write_buf(r, r->su.args.h, 0, &g, sizeof(g));
   if (rc != 0) return set_error("setup argument upload failed");
   if (!r->set_tag) return set_error("the driver has no vx_hip_set_launch_tag");
   // one untimed run: no timing events between the steps (each costs the
@@ -581,10 +580,7 @@ int set_light(rt_renderer* r, const float light[3], uint32_t* launches) {
   }
   // the render arguments' light, in stream order behind the queued frames --
   // unless every frame carries it in its launch words (rt_render_start)
-  const int rc = r->set_words ? 0
-                 : r->copy_async
-                     ? r->copy_async(r->args, a.light, offsetof(rt_kernel_arg_t, light), sizeof(a.light))
-                     : vx_copy_to_dev(r->args, a.light, offsetof(rt_kernel_arg_t, light), sizeof(a.light));
+  const int rc = r->set_words ? 0 : write_args(r, offsetof(rt_kernel_arg_t, light), a.light, sizeof(a.light));
   if (rc != 0) return set_error("light upload failed");
   if (!r->sl_mode) return 0;  // this configuration's shadow rays walk the BVH
   if (r->sl_defer > 0) {
@@ -597,10 +593,8 @@ int set_light(rt_renderer* r, const float light[3], uint32_t* launches) {
     // without them the argument block's slist_on is cleared in stream order
     if (a.slist_on && !r->set_words) {
       a.slist_on = 0;
-      const size_t o = offsetof(rt_kernel_arg_t, slist_on);
-      const int rs = r->copy_async ? r->copy_async(r->args, &a.slist_on, o, sizeof(a.slist_on))
-                                   : vx_copy_to_dev(r->args, &a.slist_on, o, sizeof(a.slist_on));
-      if (rs != 0) return set_error("slist_on upload failed");
+      if (write_args(r, offsetof(rt_kernel_arg_t, slist_on), &a.slist_on, sizeof(a.slist_on)) != 0)
+        return set_error("slist_on upload failed");
     }
     a.slist_on = 0;  // (the host's view: the lists are not in use)
     r->sl_stale = true;

@@ -74,6 +74,15 @@ int upload_image(rt_renderer* r, const std::string& path, vx_buffer_h* out) {
   return fail("cannot upload kernel " + path);
 }
 
+// free a buffer that queued launches may still use: once they have run; *buf null: nothing to do
+int release_idle(rt_renderer* r, vx_buffer_h* buf) {
+  if (!*buf) return 0;
+  if (vx_ready_wait(r->dev, VX_MAX_TIMEOUT) != 0) return fail("vx_ready_wait failed");
+  vx_mem_free(*buf);
+  *buf = nullptr;
+  return 0;
+}
+
 double ms_since(std::chrono::steady_clock::time_point t0) {
   return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
 }
@@ -593,8 +602,7 @@ static int set_several_lights(rt_renderer_h r, const float (*lights)[3], uint32_
     la.l[i].slist_addr = l.slist_addr;
     if (l.built && ((l.sidx_addr | l.slist_addr) >> 32) != 0) return fail("light-space lists above 4 GiB");
   }
-  if (r->copy_async ? r->copy_async(r->args, &la, RT_LIGHTS_ARG_OFFSET, sizeof(la)) != 0
-                    : vx_copy_to_dev(r->args, &la, RT_LIGHTS_ARG_OFFSET, sizeof(la)) != 0)
+  if (rtapp::write_args(r, RT_LIGHTS_ARG_OFFSET, &la, sizeof(la)) != 0)
     return fail("light table upload failed");
   if (vx_ready_wait(r->dev, VX_MAX_TIMEOUT) != 0) return fail("vx_ready_wait failed");
   r->nlights = n;
@@ -1258,27 +1266,15 @@ int rt_renderer_configure(rt_renderer_h r, const rt_render_params_t* p) {
     if (*b) { vx_mem_free(*b); *b = nullptr; }
   // a configure ends accumulation (rt_renderer_accum_begin): the records go, once the
   // launches still writing them have run
-  if (r->accum) {
-    if (vx_ready_wait(r->dev, VX_MAX_TIMEOUT) != 0) return fail("vx_ready_wait failed");
-    vx_mem_free(r->accum);
-    r->accum = nullptr;
-  }
+  if (release_idle(r, &r->accum) != 0) return -1;
   r->accum_on = r->accum_reset = false;
   r->accum_bytes = 0;
   r->accum_n = 0;
   // and releases the visibility records (rt_render_aov_start), the same way
-  if (r->aov) {
-    if (vx_ready_wait(r->dev, VX_MAX_TIMEOUT) != 0) return fail("vx_ready_wait failed");
-    vx_mem_free(r->aov);
-    r->aov = nullptr;
-  }
+  if (release_idle(r, &r->aov) != 0) return -1;
   r->aov_bytes = 0;
   // and the base colours of a relight capture; the capture itself is over
-  if (r->relight_base) {
-    if (vx_ready_wait(r->dev, VX_MAX_TIMEOUT) != 0) return fail("vx_ready_wait failed");
-    vx_mem_free(r->relight_base);
-    r->relight_base = nullptr;
-  }
+  if (release_idle(r, &r->relight_base) != 0) return -1;
   r->relight_base_bytes = 0;
   r->relight_n = 0;
   r->nlights = 0;  // a configure returns to one light (rt_renderer_set_lights)
@@ -1509,8 +1505,7 @@ int rt_renderer_configure(rt_renderer_h r, const rt_render_params_t* p) {
   if (!r->args &&
       upload(r->dev, nullptr, RT_RELIGHT_ARG_OFFSET + sizeof(rt_relight_arg_t), &r->args, &args_addr))
     return -1;
-  if (r->copy_async ? r->copy_async(r->args, &a, 0, sizeof(a)) != 0
-                    : vx_copy_to_dev(r->args, &a, 0, sizeof(a)) != 0)
+  if (rtapp::write_args(r, 0, &a, sizeof(a)) != 0)
     return fail("render argument upload failed");
   // The background tier: primary + shadow frames of the list image with the chunk table over
   // every chunk, not compact / sharded / path (runtime/bg_tier.h eligible; neither the generic
@@ -1550,8 +1545,7 @@ int rt_renderer_configure(rt_renderer_h r, const rt_render_params_t* p) {
         !(ble && std::atoi(ble) == 0) &&
         rtapp::bg_layers(r, r->bg_first, &ta.bglayer_addr, &launches) != 0)
       return -1;
-    if (r->copy_async ? r->copy_async(r->args, &ta, RT_TIER_ARG_OFFSET, sizeof(ta)) != 0
-                      : vx_copy_to_dev(r->args, &ta, RT_TIER_ARG_OFFSET, sizeof(ta)) != 0)
+    if (rtapp::write_args(r, RT_TIER_ARG_OFFSET, &ta, sizeof(ta)) != 0)
       return fail("render argument upload failed");
   }
   r->setup.device = device ? 1u : 0u;
@@ -1696,8 +1690,7 @@ int rt_renderer_accum_begin(rt_renderer_h r) {
     rt_accum_arg_t aa{};
     aa.accum_addr = addr;
     // behind the launches in flight, ahead of every launch started after it
-    if (r->copy_async ? r->copy_async(r->args, &aa, sizeof(rt_kernel_arg_t), sizeof(aa)) != 0
-                      : vx_copy_to_dev(r->args, &aa, sizeof(rt_kernel_arg_t), sizeof(aa)) != 0)
+    if (rtapp::write_args(r, sizeof(rt_kernel_arg_t), &aa, sizeof(aa)) != 0)
       return fail("accumulation argument upload failed");
   }
   r->accum_on = true;
@@ -1794,8 +1787,7 @@ static int aov_records(rt_renderer_h r) {
   rt_aov_arg_t aa{};
   aa.aov_addr = addr;
   // behind the launches in flight (they read the areas in front), ahead of every launch started after it
-  if (r->copy_async ? r->copy_async(r->args, &aa, RT_AOV_ARG_OFFSET, sizeof(aa)) != 0
-                    : vx_copy_to_dev(r->args, &aa, RT_AOV_ARG_OFFSET, sizeof(aa)) != 0)
+  if (rtapp::write_args(r, RT_AOV_ARG_OFFSET, &aa, sizeof(aa)) != 0)
     return fail("visibility record argument upload failed");
   return 0;
 }
@@ -1881,8 +1873,7 @@ int rt_relight_capture_start(rt_renderer_h r) {
     r->relight_base_bytes = r->cbuf_bytes;
     ra.npix = (uint32_t)npix;
     ra.cbuf1_off = r->cbuf1_off;
-    if (r->copy_async ? r->copy_async(r->args, &ra, RT_RELIGHT_ARG_OFFSET, sizeof(ra)) != 0
-                      : vx_copy_to_dev(r->args, &ra, RT_RELIGHT_ARG_OFFSET, sizeof(ra)) != 0)
+    if (rtapp::write_args(r, RT_RELIGHT_ARG_OFFSET, &ra, sizeof(ra)) != 0)
       return fail("relight argument upload failed");
   }
   if (const int e = aov_launch(r, r->aov_base_img)) return e;
@@ -2305,8 +2296,7 @@ static int build_sah(rt_renderer_h r, rt_bvh_build_stats_t* st) {
   a.nodes4_addr = nodes4_addr;
   a.n = n;
   auto copy = [&](vx_buffer_h h, const void* src, uint64_t o, uint64_t size) -> int {
-    const int rc = r->copy_async ? r->copy_async(h, src, o, size) : vx_copy_to_dev(h, src, o, size);
-    return rc == 0 ? 0 : fail("vx_copy_to_dev failed");
+    return rtapp::write_buf(r, h, o, src, size) == 0 ? 0 : fail("vx_copy_to_dev failed");
   };
   const std::vector<uint32_t> ctl0(SAH_CTL_WORDS, 0u);
   if (copy(r->su.sah.h, verts.data(), a.verts_addr - r->su.sah.addr, verts.size() * 4) ||

@@ -271,6 +271,15 @@ int upload(vx_device_h dev, const void* data, uint64_t size, vx_buffer_h* buf, u
 // a message "`who`: no <file> next to <anchor>" when one is not next to its anchor, -1 (and
 // none of the group loaded) when an upload fails
 int load_images(rt_renderer* r, rtimg::Group group, const char* who = "");
+// `size` bytes at `src` into buffer h at `offset`: in stream order behind the queued launches
+// where the driver has the asynchronous copy, else vx_copy_to_dev; the copy's return code
+inline int write_buf(rt_renderer* r, vx_buffer_h h, uint64_t offset, const void* src, uint64_t size) {
+  return r->copy_async ? r->copy_async(h, src, offset, size) : vx_copy_to_dev(h, src, offset, size);
+}
+// the same into an area of the render argument buffer (rt_common.h RT_*_ARG_OFFSET)
+inline int write_args(rt_renderer* r, uint64_t offset, const void* src, uint64_t size) {
+  return write_buf(r, r->args, offset, src, size);
+}
 
 struct DevBuf {  // scratch buffer freed at scope exit
   vx_buffer_h h = nullptr;

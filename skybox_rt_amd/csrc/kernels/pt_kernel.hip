@@ -48,7 +48,6 @@
 #if PT_MODE != 1
 #error "PT_LIGHTS is for the one-kernel per-lane form (PT_MODE 1)"
 #endif
-#define RT_LIGHTS 1  // rt_trace.h: lights_args, occluded_list / occluded_list_coop on a light's own lists
 #undef PT_PAIR
 #define PT_PAIR 0
 #endif
@@ -318,6 +317,15 @@ __device__ __forceinline__ void path_hit(const Scene& S, PathState& st, const fl
 #define PT_ACC(slot, v) do {} while (0)
 #endif
 
+// the direct-light segment from a path vertex P to a light
+__device__ __forceinline__ void light_segment(const float P[3], const float light[3], Ray& s) {
+  s.o[0] = P[0]; s.o[1] = P[1]; s.o[2] = P[2];
+  s.d[0] = light[0] - P[0];
+  s.d[1] = light[1] - P[1];
+  s.d[2] = light[2] - P[2];
+  ray_setup(s);
+}
+
 // One path vertex for an active lane: direct light through a shadow ray,
 // then (v < bounces) the bounce; returns whether the path continues (st then
 // describes the next vertex), else the pixel is final.  Every lane of the
@@ -350,12 +358,9 @@ __device__ __forceinline__ bool path_step(const Scene& S, int32_t* stack, PathSt
   const uint32_t nl = lights_count(S), sn = LA->slist_n;
   const uint64_t c0 = PT_CYC();
   for (uint32_t i = 0; i < nl; ++i) {
+    const float L[3] = {LA->l[i].light[0], LA->l[i].light[1], LA->l[i].light[2]};
     Ray s;
-    s.o[0] = P[0]; s.o[1] = P[1]; s.o[2] = P[2];
-    s.d[0] = LA->l[i].light[0] - P[0];
-    s.d[1] = LA->l[i].light[1] - P[1];
-    s.d[2] = LA->l[i].light[2] - P[2];
-    ray_setup(s);
+    light_segment(P, L, s);
     cnt.shadow += act ? one : 0u;
     const uint32_t sidx = (uint32_t)LA->l[i].sidx_addr, slist = (uint32_t)LA->l[i].slist_addr;
     const bool occ = CO == 1 ? occluded_list_coop(S, s, act, st.pid, hi, cnt, sidx, slist, sn)
@@ -380,11 +385,7 @@ __device__ __forceinline__ bool path_step(const Scene& S, int32_t* stack, PathSt
 #else
   // direct light: shadow segment P -> light
   Ray s;
-  s.o[0] = P[0]; s.o[1] = P[1]; s.o[2] = P[2];
-  s.d[0] = S.light[0] - P[0];
-  s.d[1] = S.light[1] - P[1];
-  s.d[2] = S.light[2] - P[2];
-  ray_setup(s);
+  light_segment(P, S.light, s);
   cnt.shadow += act ? one : 0u;
   float ts;
   const uint64_t c0 = PT_CYC();
@@ -671,11 +672,7 @@ __device__ __forceinline__ void queued_path(const vx_task_t& task, const Scene& 
 // launch), the 8-bit sample values are summed in registers, the record is
 // written once and the framebuffer gets the rounded mean.
 __device__ __forceinline__ uint32_t accum_buf(const Scene& S) {
-  uint64_t p = S.argp + sizeof(rt_kernel_arg_t);
-  asm volatile("" : "+s"(p));  // opaque, as task_args: read where used
-  const __attribute__((address_space(4))) rt_accum_arg_t* a =
-      (const __attribute__((address_space(4))) rt_accum_arg_t*)p;
-  return (uint32_t)a->accum_addr;
+  return (uint32_t)arg_at<rt_accum_arg_t>(S, sizeof(rt_kernel_arg_t))->accum_addr;  // as task_args: read where used
 }
 __device__ __forceinline__ uint4 accum_load(const Scene& S, uint32_t abuf, uint32_t out) {
   if (S.lw3 & RT_LW_ACCUM_RESET) return make_uint4(0u, 0u, 0u, 0u);
@@ -916,8 +913,6 @@ __device__ __forceinline__ void lane_path(const vx_task_t& task, const Scene& S,
 }
 #endif
 
-__device__ __forceinline__ void flush(int slot, uint32_t v) { vx_mpm_add(RT_MPM_USER + slot, v); }
-
 }  // namespace
 
 // grid for the driver: 128 64-thread blocks per CU (32768), one 64-task chunk
@@ -1002,10 +997,7 @@ VX_MAIN(rt_kernel_arg_t, arg, PT_BLOCK) {
 #endif
 #endif
 #ifndef RT_STAMPS  // the stamp image keeps slots 4-6 for its cycle accumulators
-  flush(RT_STAT_PRIMARY, cnt.primary);
-  flush(RT_STAT_SHADOW, cnt.shadow);
-  flush(RT_STAT_HITS, cnt.hits);
-  flush(RT_STAT_OCCLUDED, cnt.occluded);
+  flush_rays(cnt);
   flush(RT_STAT_BOUNCE, cnt.bounce);
 #endif
 #ifdef RT_STAMPS

@@ -20,8 +20,8 @@
 // Binning (gfxutil.cpp:237-271) happens in the workgroup: each chunk of 256
 // primitives is bbox-tested against the tile in parallel and compacted in
 // order (ballot + mbcnt + a 4-wave prefix in LDS) into the tile's list; the
-// listed primitives' records are wave-uniform and come in through the scalar
-// cache.  One launch renders every drawcall of the frame.
+// listed primitives' records are staged in LDS during binning and read back
+// as broadcasts.  One launch renders every drawcall of the frame.
 #include <hip/hip_runtime.h>
 
 #include "gfx_device.h"
@@ -38,17 +38,11 @@ __device__ __forceinline__ uint32_t lane_id() {
   return __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
 }
 
-#ifndef RS_STAGE
-#define RS_STAGE 1  // 1: listed primitives' records staged in LDS during binning
-#endif
-
 struct RsLds {
   uint32_t list[RS_BLOCK];   // the tile's primitives (global pids) of one chunk, in order
   uint2 bb[RS_BLOCK];        // their screen boxes (per-pixel bin test, bins finer than the tile)
   uint32_t wave_n[kWaves];
-#if RS_STAGE
-  uint4 rec[RS_BLOCK][8];    // their rt_prim_t records (128 B each), same order
-#endif
+  uint4 rec[RS_BLOCK][8];    // their rt_prim_t records (128 B each), staged during binning, same order
 };
 
 struct Frame {
@@ -136,25 +130,19 @@ __device__ __forceinline__ void render_tile(const Frame& F, uint32_t tile, RsLds
                                                      __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
         L.list[pre + r] = g;
         L.bb[pre + r] = bb;
-#if RS_STAGE
 #pragma unroll
         for (int k = 0; k < 8; ++k) L.rec[pre + r][k] = F.A.ld_u4(F.prims + 128u * g + 16u * k);
-#endif
       }
       __syncthreads();
       // rasterize the listed primitives in order
       for (uint32_t k = 0; k < n; ++k) {
         gfx::Prim p;
-#if RS_STAGE
 #pragma unroll
         for (int i = 0; i < 8; ++i) {  // broadcast LDS reads
           const uint4 v = L.rec[k][i];
           p.w[4 * i + 0] = (int32_t)v.x; p.w[4 * i + 1] = (int32_t)v.y;
           p.w[4 * i + 2] = (int32_t)v.z; p.w[4 * i + 3] = (int32_t)v.w;
         }
-#else
-        gfx::load_prim<true>(F.A, F.prims + 128u * L.list[k], p);
-#endif
 #pragma unroll
         for (uint32_t j = 0; j < 4; ++j) {
           if (j >= npx) break;

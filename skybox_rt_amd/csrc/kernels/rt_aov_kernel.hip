@@ -22,9 +22,7 @@
 // the scalar cache.  The record buffer's address stands behind the table
 // (rt_aov_arg_t).
 //
-// Image rt_aov (Makefile): the binary16 BVH4 only (RT_ONLY_BVH4H), built with
-// RT_LIGHTS for rt_trace.h's shadow_ray / occluded_list forms that take the
-// light and its lists as parameters.
+// Image rt_aov (Makefile): the binary16 BVH4 only (RT_ONLY_BVH4H).
 //
 // Image rt_aov_base (RT_AOV_BASE=1; vx_rt.h rt_relight_capture_start): the same
 // launch, the same records, and the pixel shaded without shadows -- shade_wave
@@ -42,8 +40,8 @@
 #define VX_BLOCK_THREADS RT_BLOCK_THREADS  // vx_spawn.h: the workgroup size as a constant
 #include "rt_trace.h"
 
-#if !RT_ONLY_BVH4H || !RT_LIGHTS
-#error "rt_aov_kernel.hip walks the binary16 BVH4 only, with the light-parameter forms (build with -DRT_ONLY_BVH4H=1 -DRT_LIGHTS=1)"
+#if !RT_ONLY_BVH4H
+#error "rt_aov_kernel.hip walks the binary16 BVH4 only (build with -DRT_ONLY_BVH4H=1)"
 #endif
 
 namespace {
@@ -52,33 +50,15 @@ using namespace rtk;
 
 // the record buffer as an arena offset (rt_app checks it lies below 4 GiB)
 __device__ __forceinline__ uint32_t aov_base(const Scene& S) {
-  uint64_t p = S.argp + RT_AOV_ARG_OFFSET;
-  asm volatile("" : "+s"(p));
-  return (uint32_t)((const __attribute__((address_space(4))) rt_aov_arg_t*)p)->aov_addr;
+  return (uint32_t)arg_at<rt_aov_arg_t>(S, RT_AOV_ARG_OFFSET)->aov_addr;
 }
 
 #if RT_AOV_BASE
 // the base-colour buffer, the same way
 __device__ __forceinline__ uint32_t base_colours(const Scene& S) {
-  uint64_t p = S.argp + RT_RELIGHT_ARG_OFFSET;
-  asm volatile("" : "+s"(p));
-  return (uint32_t)((const __attribute__((address_space(4))) rt_relight_arg_t*)p)->base_addr;
+  return (uint32_t)arg_at<rt_relight_arg_t>(S, RT_RELIGHT_ARG_OFFSET)->base_addr;
 }
 #endif
-
-// The winner's depth word after the packet walk of the tree (no block lists),
-// which returns the pid only: the word vis_test computed for it, from the same
-// edge functions and z attribute (rt_om_kernel.hip winner_depth).
-__device__ __forceinline__ uint32_t winner_depth(const Scene& S, int32_t hit, uint32_t x, uint32_t y) {
-  if (hit < 0) return VX_OM_DEPTH_MASK;
-  const uint32_t o = S.prims + 128u * (uint32_t)hit;
-  const uint4 A = S.A.ld_u4(o), B = S.A.ld_u4(o + 16), C = S.A.ld_u4(o + 32);
-  const int32_t e0[3] = {(int32_t)A.x, (int32_t)A.y, (int32_t)A.z};
-  const int32_t e1[3] = {(int32_t)A.w, (int32_t)B.x, (int32_t)B.y};
-  const int32_t e2[3] = {(int32_t)B.z, (int32_t)B.w, (int32_t)C.x};
-  const int32_t z3[3] = {(int32_t)C.y, (int32_t)C.z, (int32_t)C.w};
-  return vis_depth(gfx::edge_eval(e0, x, y), gfx::edge_eval(e1, x, y), gfx::edge_eval(e2, x, y), z3);
-}
 
 // one light's verdict for the wave's shadow rays: true where the light does not see the lane's point
 __device__ __forceinline__ bool light_occluded(const Scene& S, const Ray& p, float th, const float L[3],
@@ -106,15 +86,8 @@ __device__ __forceinline__ void kernel_body(const vx_task_t& task, const Scene& 
   const bool tie_high = (S.flags & RT_FLAG_TIE_HIGH) != 0;
 
   // primary visibility, the winner's depth word kept
-  int32_t hit;
   uint32_t hz;
-  if (rt_usgpr(S.blist_blocks)) {
-    hit = block_primary_z(S, block_header(S, lb), x, y, in, tie_high, cnt, &hz);
-  } else {
-    const int32_t h = trace_primary_packet(walk_scene(S), x, y, in, tie_high, cnt);
-    hit = in ? h : -1;
-    hz = winner_depth(S, hit, x, y);
-  }
+  const int32_t hit = primary_z(S, lb, x, y, in, tie_high, cnt, &hz);
   cnt.hits += hit >= 0;
   const int32_t spid = resolve_layers(S, x, y, in && hit < 0, hit, cnt);
 #if RT_AOV_BASE
@@ -133,6 +106,8 @@ __device__ __forceinline__ void kernel_body(const vx_task_t& task, const Scene& 
     if (__ballot(shadow) != 0) {
       df |= shadow ? RT_AOV_SHADOW_RAY : 0u;
       if (nl < 2) {
+        // (the scene's own light through the same call as a light of the table: written with the plain
+        // shadow_ray / occluded_list overloads the branch compiles to other code)
         const float L[3] = {S.light[0], S.light[1], S.light[2]};
         mask = light_occluded(S, r, th, L, shadow, hit, S.slist_on, S.sidx, S.slist, S.slist_n, cnt) ? 1u : 0u;
       } else {
@@ -152,8 +127,6 @@ __device__ __forceinline__ void kernel_body(const vx_task_t& task, const Scene& 
   if (in) S.A.st_u4(aov + 16u * out, make_uint4((uint32_t)spid, df, __float_as_uint(th), mask));
 }
 
-__device__ __forceinline__ void flush(int slot, uint32_t v) { vx_mpm_add(RT_MPM_USER + slot, v); }
-
 }  // namespace
 
 VX_MAIN(rt_kernel_arg_t, arg, RT_BLOCK_THREADS) {
@@ -170,9 +143,6 @@ VX_MAIN(rt_kernel_arg_t, arg, RT_BLOCK_THREADS) {
   const int rc = vx_spawn_tasks(
       S.num_tasks, [&](const vx_task_t& task, const Scene* s) { kernel_body(task, *s, nl, aov, base, cnt); }, &S);
   // a frame's primary rays and hits; the shadow rays of every light, the masks' set bits
-  flush(RT_STAT_PRIMARY, cnt.primary);
-  flush(RT_STAT_SHADOW, cnt.shadow);
-  flush(RT_STAT_HITS, cnt.hits);
-  flush(RT_STAT_OCCLUDED, cnt.occluded);
+  flush_rays(cnt);
   return rc;
 }

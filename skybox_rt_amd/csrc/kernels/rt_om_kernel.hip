@@ -53,10 +53,7 @@ struct Tail {
   uint32_t oidx, olist, ovtris, base, oms;
 };
 __device__ __forceinline__ Tail tail_args(const Scene& S) {
-  uint64_t p = S.argp;
-  asm volatile("" : "+s"(p));
-  const __attribute__((address_space(4))) rt_kernel_arg_t* a =
-      (const __attribute__((address_space(4))) rt_kernel_arg_t*)p;
+  const auto* a = arg_at(S);
   Tail t;
   t.oidx = (uint32_t)a->oidx_addr;
   t.olist = (uint32_t)a->olist_addr;
@@ -95,21 +92,6 @@ __device__ __forceinline__ rt_omstate_t om_state(const OmWords& o) {
   return s;
 }
 
-// The winner's depth word after the packet walk of the tree (no block lists:
-// env RT_BLOCK_LISTS=0, or lists that did not fit), which returns the pid
-// only: the word vis_test computed for it, from the same edge functions and
-// z attribute (MakeVisTri copies both out of the rt_prim_t record).
-__device__ __forceinline__ uint32_t winner_depth(const Scene& S, int32_t hit, uint32_t x, uint32_t y) {
-  if (hit < 0) return VX_OM_DEPTH_MASK;
-  const uint32_t o = S.prims + 128u * (uint32_t)hit;
-  const uint4 A = S.A.ld_u4(o), B = S.A.ld_u4(o + 16), C = S.A.ld_u4(o + 32);
-  const int32_t e0[3] = {(int32_t)A.x, (int32_t)A.y, (int32_t)A.z};
-  const int32_t e1[3] = {(int32_t)A.w, (int32_t)B.x, (int32_t)B.y};
-  const int32_t e2[3] = {(int32_t)B.z, (int32_t)B.w, (int32_t)C.x};
-  const int32_t z3[3] = {(int32_t)C.y, (int32_t)C.z, (int32_t)C.w};
-  return vis_depth(gfx::edge_eval(e0, x, y), gfx::edge_eval(e1, x, y), gfx::edge_eval(e2, x, y), z3);
-}
-
 __device__ __forceinline__ void kernel_body(const vx_task_t& task, const Scene& S, Counters& cnt) {
   const uint32_t t = task.blockIdx.x;
   // the chunk's task map in scalar registers (every lane runs the same chunk)
@@ -123,15 +105,8 @@ __device__ __forceinline__ void kernel_body(const vx_task_t& task, const Scene& 
   const bool tie_high = (S.flags & RT_FLAG_TIE_HIGH) != 0;
 
   // ---- the traced head: rt_kernel's frame, the winner's depth word kept ----
-  int32_t hit;
   uint32_t hz;
-  if (rt_usgpr(S.blist_blocks)) {
-    hit = block_primary_z(S, block_header(S, lb), x, y, in, tie_high, cnt, &hz);
-  } else {
-    const int32_t h = trace_primary_packet(walk_scene(S), x, y, in, tie_high, cnt);
-    hit = in ? h : -1;
-    hz = winner_depth(S, hit, x, y);
-  }
+  const int32_t hit = primary_z(S, lb, x, y, in, tie_high, cnt, &hz);
   cnt.hits += hit >= 0;
   const int32_t spid = resolve_layers(S, x, y, in && hit < 0, hit, cnt);
   uint32_t color = shade_wave(S, spid, x, y, S.clear_color, cnt);
@@ -208,8 +183,6 @@ __device__ __forceinline__ void kernel_body(const vx_task_t& task, const Scene& 
   if (in) store_out(S, out, color);
 }
 
-__device__ __forceinline__ void flush(int slot, uint32_t v) { vx_mpm_add(RT_MPM_USER + slot, v); }
-
 }  // namespace
 
 VX_MAIN(rt_kernel_arg_t, arg, RT_BLOCK_THREADS) {
@@ -218,9 +191,6 @@ VX_MAIN(rt_kernel_arg_t, arg, RT_BLOCK_THREADS) {
   const int rc = vx_spawn_tasks(
       S.num_tasks, [&](const vx_task_t& task, const Scene* s) { kernel_body(task, *s, cnt); }, &S);
   // the head's rays, as rt_kernel counts them
-  flush(RT_STAT_PRIMARY, cnt.primary);
-  flush(RT_STAT_SHADOW, cnt.shadow);
-  flush(RT_STAT_HITS, cnt.hits);
-  flush(RT_STAT_OCCLUDED, cnt.occluded);
+  flush_rays(cnt);
   return rc;
 }

@@ -1,5 +1,7 @@
 // rt_trace.h -- device pieces shared by the RT kernel programs
-// (rt_kernel.hip: primary + shadow rays; pt_kernel.hip: diffuse path trace):
+// (rt_kernel.hip: primary + shadow rays; rt_flat_kernel.hip: the same over
+// the flat list; pt_kernel.hip: diffuse path trace; rt_om_kernel.hip and
+// rt_aov_kernel.hip: the per-pixel images):
 // scene arguments, ray setup, Möller–Trumbore, slab test, the per-lane BVH
 // walk (closest hit / any hit, stack in LDS) and the wave-packet walks
 // (primary visibility, shadow rays; stack in one VGPR), the per-block
@@ -58,17 +60,6 @@
 #ifndef RT_CHUNK_DESC
 #define RT_CHUNK_DESC 0
 #endif
-//   RT_LIGHTS      images rt_lights / rt_lights_stats: a frame lit by the lights
-//                  of the table behind the argument block (rt_common.h
-//                  rt_lights_arg_t), every queued shadow ray tested against
-//                  each of them in one drain (rt_kernel.hip shadow_drain);
-//                  shadow_ray and occluded_list then take the light and its
-//                  list bases as parameters (occluded_list_coop too: the path
-//                  tracer's images pt_lights / pt_lights_accum, pt_kernel.hip
-//                  PT_LIGHTS, read the same table at every path vertex)
-#ifndef RT_LIGHTS
-#define RT_LIGHTS 0
-#endif
 
 namespace rtk {
 
@@ -117,6 +108,31 @@ struct Scene {
 // by one and asserts this size, so a new field cannot be left out unnoticed
 #define RT_SCENE_TAIL_BYTES 192
 
+// The argument buffer is read through the scalar cache (constant address
+// space, wave-uniform address), by one of two accessors:
+//   arg_at<T>(S, off)     the area at `off` behind S.argp, read where it is
+//                         used: the address passes through an opaque SGPR, so
+//                         the loads are issued at the call, not hoisted to the
+//                         wave's start or merged with another site's
+//   arg_entry<T>(p, off)  a generic pointer at kernel entry, made wave-uniform
+//                         (readfirstlane returns int: through uint32_t, or the
+//                         low word sign-extends)
+template <typename T>
+using arg_ptr = const __attribute__((address_space(4))) T*;
+template <typename T = rt_kernel_arg_t>
+__device__ __forceinline__ arg_ptr<T> arg_at(const Scene& S, uint32_t off = 0) {
+  uint64_t p = S.argp + off;
+  asm volatile("" : "+s"(p));
+  return (arg_ptr<T>)p;
+}
+template <typename T = rt_kernel_arg_t>
+__device__ __forceinline__ arg_ptr<T> arg_entry(const void* ga, uint32_t off = 0) {
+  const uint64_t p = (uint64_t)ga + off;
+  const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)p);
+  const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(p >> 32));
+  return (arg_ptr<T>)(((uint64_t)hi << 32) | (uint64_t)lo);
+}
+
 // The argument block is read through the scalar cache (constant address
 // space, wave-uniform address): the scene's fields then live in SGPRs, and
 // the traversal loops form node / triangle addresses in scalar registers
@@ -130,13 +146,7 @@ struct Scene {
 // cbuf + offset formed here instead stayed live across the chunk loop and
 // cost rt_kernel 24 more SGPR spills and 36 B of scratch.
 __device__ __forceinline__ Scene load_scene(const rt_kernel_arg_t* ga, const vx_launch_words_t& lw) {
-  const uint64_t p = (uint64_t)ga;
-  // (readfirstlane returns int: through uint32_t, or the low word sign-extends)
-  const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)p);
-  const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(p >> 32));
-  const uint64_t u = ((uint64_t)hi << 32) | (uint64_t)lo;
-  const __attribute__((address_space(4))) rt_kernel_arg_t* a =
-      (const __attribute__((address_space(4))) rt_kernel_arg_t*)u;
+  const auto* a = arg_entry(ga);
   Scene s;
   s.argp = (uint64_t)a;
   s.A = vx_arena::get();
@@ -228,10 +238,7 @@ __device__ __forceinline__ Scene walk_scene(const Scene& S) {
 #undef RT_COPY
   // (the walks shoot no ray of their own: primary_dir / shadow_ray's fields stay out of the copy)
   w.sx = w.sy = w.light[0] = w.light[1] = w.light[2] = 0.0f;
-  uint64_t p = S.argp;
-  asm volatile("" : "+s"(p));
-  const __attribute__((address_space(4))) rt_kernel_arg_t* a =
-      (const __attribute__((address_space(4))) rt_kernel_arg_t*)p;
+  const auto* a = arg_at(S);
   w.nodes = (uint32_t)a->nodes_addr;
   w.nodes4 = (uint32_t)a->nodes4_addr;
   w.tris = (uint32_t)a->tris_addr;
@@ -841,8 +848,8 @@ __device__ __forceinline__ uint32_t slist_cell(const Ray& s, uint32_t N) {
 __device__ __forceinline__ float slist_limit(const Ray& s) {
   return (s.d[0] * s.d[0] + s.d[1] * s.d[1] + s.d[2] * s.d[2]) * 1.001f;
 }
-#if RT_LIGHTS
-// (the lists of one light of the table: their index and entries, at n cells per face side)
+// (the lists of one light: their index and entries, at slist_n cells per face side -- a light of
+// the table behind the argument block, or, the overload below, the scene's own)
 __device__ __forceinline__ bool occluded_list(const Scene& S, const Ray& s, bool act, int32_t skip,
                                               Counters& cnt, uint32_t sidx, uint32_t slist, uint32_t slist_n) {
   if (!act) return false;
@@ -850,15 +857,6 @@ __device__ __forceinline__ bool occluded_list(const Scene& S, const Ray& s, bool
   const uint32_t off = S.A.ld_u32(sidx + 8u * cell), n = S.A.ld_u32(sidx + 8u * cell + 4u);
   const float lim = slist_limit(s);
   uint32_t o = slist + 48u * off;
-#else
-__device__ __forceinline__ bool occluded_list(const Scene& S, const Ray& s, bool act, int32_t skip,
-                                              Counters& cnt) {
-  if (!act) return false;
-  const uint32_t cell = slist_cell(s, S.slist_n);
-  const uint32_t off = S.A.ld_u32(S.sidx + 8u * cell), n = S.A.ld_u32(S.sidx + 8u * cell + 4u);
-  const float lim = slist_limit(s);
-  uint32_t o = S.slist + 48u * off;
-#endif
   for (uint32_t q = 0; q < n; q += 2, o += 96u) {
     float4 t[6];
 #pragma unroll
@@ -875,6 +873,10 @@ __device__ __forceinline__ bool occluded_list(const Scene& S, const Ray& s, bool
     }
   }
   return false;
+}
+__device__ __forceinline__ bool occluded_list(const Scene& S, const Ray& s, bool act, int32_t skip,
+                                              Counters& cnt) {
+  return occluded_list(S, s, act, skip, cnt, S.sidx, S.slist, S.slist_n);
 }
 
 // Cooperative walks for the path tracer's 32-pixel waves (pt_kernel
@@ -1162,8 +1164,7 @@ __device__ __forceinline__ int32_t trace_coop(const Scene& S, const Ray& r, int3
 // testing the first two, the upper the other two; the verdict is whether any
 // record occludes (order-free), the tests counted are the sequential scan's
 // (the upper lane's only when the lower lane's two did not occlude)
-#if RT_LIGHTS
-// (the lists of one light of the table, as occluded_list takes them)
+// (the lists of one light, as occluded_list takes them)
 __device__ __forceinline__ bool occluded_list_coop(const Scene& S, const Ray& s, bool act, int32_t skip,
                                                    bool hi, Counters& cnt, uint32_t sidx, uint32_t slist,
                                                    uint32_t slist_n) {
@@ -1173,16 +1174,6 @@ __device__ __forceinline__ bool occluded_list_coop(const Scene& S, const Ray& s,
   const uint32_t e0 = hi ? 2u : 0u;
   const float lim = slist_limit(s);
   uint32_t o = slist + 48u * (off + e0);
-#else
-__device__ __forceinline__ bool occluded_list_coop(const Scene& S, const Ray& s, bool act, int32_t skip,
-                                                   bool hi, Counters& cnt) {
-  if (!act) return false;
-  const uint32_t cell = slist_cell(s, S.slist_n);
-  const uint32_t off = S.A.ld_u32(S.sidx + 8u * cell), n = S.A.ld_u32(S.sidx + 8u * cell + 4u);
-  const uint32_t e0 = hi ? 2u : 0u;
-  const float lim = slist_limit(s);
-  uint32_t o = S.slist + 48u * (off + e0);
-#endif
   for (uint32_t q = 0; q < n; q += 4, o += 192u) {
     bool hit = false, end = false;  // end: a record past the bound (occluded_list)
     RT_CNT(uint32_t tests = 0;)
@@ -1211,6 +1202,10 @@ __device__ __forceinline__ bool occluded_list_coop(const Scene& S, const Ray& s,
     if (((ev | pev) & 2u) != 0u) return false;
   }
   return false;
+}
+__device__ __forceinline__ bool occluded_list_coop(const Scene& S, const Ray& s, bool act, int32_t skip,
+                                                   bool hi, Counters& cnt) {
+  return occluded_list_coop(S, s, act, skip, hi, cnt, S.sidx, S.slist, S.slist_n);
 }
 
 template <bool ANY>
@@ -1712,10 +1707,7 @@ struct TaskArgs {
 __device__ __forceinline__ TaskArgs task_args(const Scene& S) {
   TaskArgs t;
 #if RT_LAZY_TASK_ARGS
-  uint64_t p = S.argp;
-  asm volatile("" : "+s"(p));  // opaque: re-issued here, not hoisted or CSE'd
-  const __attribute__((address_space(4))) rt_kernel_arg_t* a =
-      (const __attribute__((address_space(4))) rt_kernel_arg_t*)p;
+  const auto* a = arg_at(S);  // opaque: re-issued here, not hoisted or CSE'd
   t.split_tiles = a->split_tiles; t.split_log = a->split_log; t.order = (uint32_t)a->order_addr;
   t.shard_index = a->shard_index; t.shard_count = a->shard_count; t.tiles_x = a->tiles_x;
   t.quad_tiles = a->quad_tiles; t.tiles_x_magic = a->tiles_x_magic;
@@ -1846,9 +1838,8 @@ __device__ __forceinline__ void primary_dir(const Scene& S, uint32_t x, uint32_t
   r.d[2] = 1.0f;
 }
 
-// shadow segment from the (eye-ward nudged) hit point to the light
-#if RT_LIGHTS
-// (to one light of the table: the origin does not depend on it)
+// shadow segment from the (eye-ward nudged) hit point to a light (the origin does not depend on
+// it): a light of the table, or the scene's own
 __device__ __forceinline__ void shadow_ray(const Scene& S, const Ray& p, float th, Ray& s, const float light[3]) {
   const float tt = th * 0.999755859375f;  // origin pulled toward the eye by 2^-12 of t
   s.o[0] = p.d[0] * tt; s.o[1] = p.d[1] * tt; s.o[2] = p.d[2] * tt;
@@ -1857,23 +1848,14 @@ __device__ __forceinline__ void shadow_ray(const Scene& S, const Ray& p, float t
   s.d[2] = light[2] - s.o[2];
   ray_setup(s);
 }
+__device__ __forceinline__ void shadow_ray(const Scene& S, const Ray& p, float th, Ray& s) {
+  shadow_ray(S, p, th, s, S.light);
+}
 // the light table, in the argument buffer behind the tier's area: read where used, through the
 // scalar cache (wave-uniform address: a light's fields live in SGPRs)
-__device__ __forceinline__ const __attribute__((address_space(4))) rt_lights_arg_t* lights_args(const Scene& S) {
-  uint64_t p = S.argp + RT_LIGHTS_ARG_OFFSET;
-  asm volatile("" : "+s"(p));
-  return (const __attribute__((address_space(4))) rt_lights_arg_t*)p;
+__device__ __forceinline__ arg_ptr<rt_lights_arg_t> lights_args(const Scene& S) {
+  return arg_at<rt_lights_arg_t>(S, RT_LIGHTS_ARG_OFFSET);
 }
-#else
-__device__ __forceinline__ void shadow_ray(const Scene& S, const Ray& p, float th, Ray& s) {
-  const float tt = th * 0.999755859375f;  // origin pulled toward the eye by 2^-12 of t
-  s.o[0] = p.d[0] * tt; s.o[1] = p.d[1] * tt; s.o[2] = p.d[2] * tt;
-  s.d[0] = S.light[0] - s.o[0];
-  s.d[1] = S.light[1] - s.o[1];
-  s.d[2] = S.light[2] - s.o[2];
-  ray_setup(s);
-}
-#endif
 
 // Path tracing in two kernels (BASELINE config 4's wave64 active-ray
 // compaction): the first pass (pt_primary, rt_kernel.hip built
@@ -1885,10 +1867,7 @@ struct PathQ {
   uint32_t q, ctr, lanes, cap;
 };
 __device__ __forceinline__ PathQ pathq_args(const Scene& S) {
-  uint64_t p = S.argp;
-  asm volatile("" : "+s"(p));
-  const __attribute__((address_space(4))) rt_kernel_arg_t* a =
-      (const __attribute__((address_space(4))) rt_kernel_arg_t*)p;
+  const auto* a = arg_at(S);
   PathQ o;
   o.q = (uint32_t)a->pathq_addr;
   o.ctr = (uint32_t)a->pathq_ctr_addr;
@@ -1929,6 +1908,43 @@ __device__ __forceinline__ void store_pixel(const Scene& S, uint32_t t, uint32_t
     idx = (m.lt << 10) | ((y & 31u) << 5) | (x & 31u);
   }
   S.A.st_u32(S.cbuf + (S.lw3 & RT_LW_CBUF_MASK) + 4u * idx, color);
+}
+
+// ---- shared by the per-pixel images (rt_om_kernel.hip, rt_aov_kernel.hip) ----
+// The winner's depth word after the packet walk of the tree (no block lists:
+// env RT_BLOCK_LISTS=0, or lists that did not fit), which returns the pid
+// only: the word vis_test computed for it, from the same edge functions and
+// z attribute (MakeVisTri copies both out of the rt_prim_t record).
+__device__ __forceinline__ uint32_t winner_depth(const Scene& S, int32_t hit, uint32_t x, uint32_t y) {
+  if (hit < 0) return VX_OM_DEPTH_MASK;
+  const uint32_t o = S.prims + 128u * (uint32_t)hit;
+  const uint4 A = S.A.ld_u4(o), B = S.A.ld_u4(o + 16), C = S.A.ld_u4(o + 32);
+  const int32_t e0[3] = {(int32_t)A.x, (int32_t)A.y, (int32_t)A.z};
+  const int32_t e1[3] = {(int32_t)A.w, (int32_t)B.x, (int32_t)B.y};
+  const int32_t e2[3] = {(int32_t)B.z, (int32_t)B.w, (int32_t)C.x};
+  const int32_t z3[3] = {(int32_t)C.y, (int32_t)C.z, (int32_t)C.w};
+  return vis_depth(gfx::edge_eval(e0, x, y), gfx::edge_eval(e1, x, y), gfx::edge_eval(e2, x, y), z3);
+}
+// primary visibility of local block lb with the winner's depth word kept: the
+// block's candidate list when the lists are on, else the packet walk of the tree
+__device__ __forceinline__ int32_t primary_z(const Scene& S, uint32_t lb, uint32_t x, uint32_t y, bool in,
+                                             bool tie_high, Counters& cnt, uint32_t* hz) {
+  if (rt_usgpr(S.blist_blocks)) return block_primary_z(S, block_header(S, lb), x, y, in, tie_high, cnt, hz);
+  const int32_t h = trace_primary_packet(walk_scene(S), x, y, in, tie_high, cnt);
+  const int32_t hit = in ? h : -1;
+  *hz = winner_depth(S, hit, x, y);
+  return hit;
+}
+
+// RT statistics go to the user MPM counters (VX_CSR_MPM_USER = 0xB03 + slot),
+// which the driver zeroes before every launch and vx_mpm_query() reads back.
+__device__ __forceinline__ void flush(int slot, uint32_t v) { vx_mpm_add(RT_MPM_USER + slot, v); }
+// the four ray counters every image reports
+__device__ __forceinline__ void flush_rays(const Counters& cnt) {
+  flush(RT_STAT_PRIMARY, cnt.primary);
+  flush(RT_STAT_SHADOW, cnt.shadow);
+  flush(RT_STAT_HITS, cnt.hits);
+  flush(RT_STAT_OCCLUDED, cnt.occluded);
 }
 
 

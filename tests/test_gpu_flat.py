@@ -1,4 +1,4 @@
-"""GPU parity of the flat-triangle-list image (rt_flat: no BVH, the geometry
+"""GPU parity of the flat-triangle-list image (rt_flat, kernels/rt_flat_kernel.hip: no BVH, the geometry
 list staged in LDS; BASELINE config 2 = 256^2 tekkaman primary rays, and
 config 1 = the 64^2 triangle) against the oracle's brute force, bit-exact
 including the per-triangle test counts, and against the BVH image."""
