@@ -190,6 +190,26 @@ int orc_shadow_lists(const orc_scene_t* scene, const float light[3], uint32_t* i
 int orc_mt(const float o[3], const float d[3], const float v0[3],
            const float e1[3], const float e2[3], float tmin, float* t_out);
 
+/* The ray routines as tables (exposed for unit tests; rt.c): the slab test of
+ * one box after the ray's setup (planes = lo.x, hi.x, lo.y, hi.y, lo.z, hi.z;
+ * returns the verdict, tnear and tfar), the path tracer's hash stream and
+ * sampler, the geometric normal. */
+int orc_slab(const float o[3], const float d[3], const float planes[6], float tmin, float tmax,
+             float* tnear, float* tfar);
+uint32_t orc_pcg_hash(uint32_t v);
+uint32_t orc_pt_key(uint32_t seed, uint32_t px, uint32_t v);
+float orc_pt_u11(uint32_t h);
+void orc_pt_bounce_dir(const float n[3], uint32_t key, float dir[3]);
+void orc_pt_normal(const float e1[3], const float e2[3], const float din[3], float n[3]);
+/* A table of n arbitrary rays (rays [n][8]: o, d, tmin, tmax; skip [n] a pid
+ * left out or -1; tie_high [n]) over the triangles tri9 [num_prims][9] (v0,
+ * e1, e2 by pid): mode 0 brute force over every triangle, 1 the BVH2 of
+ * `bvh`, 2 its BVH4.  Per ray the closest hit (pid or -1, t) and whether any
+ * hit lies below tmax. */
+int orc_trace_rays(const orc_bvh_t* bvh, const float* tri9, int32_t num_prims, int mode, uint32_t n,
+                   const float* rays, const int32_t* skip, const uint8_t* tie_high, int32_t* pid,
+                   float* t, uint8_t* occluded);
+
 /* ---- linear BVH (oracle/lbvh.c, restating kernels/bvh_build.hip) -------- */
 /* verts: [n][3][3] clip (x, y, w); geom: [n][12] rt_tri_t records of the same
  * triangles; out: nodes [max(n-1,1)][16], tris [n+3][12], depth. */

@@ -478,3 +478,127 @@ def om_app(width=128, height=128, num_tasks=256 * 32 * 64, color=0xFFFFFFFF, dep
     if rc != 0:
         raise RuntimeError(f"orc_om_app failed: {rc}")
     return cbuf.reshape(height, width)
+
+
+# ---- the ray routines as tables (oracle/rt.c orc_mt .. orc_trace_rays) -----
+def _f32rows(a, width):
+    a = np.ascontiguousarray(np.asarray(a, np.float32).reshape(-1, width))
+    return a, a.ctypes.data, a.strides[0]
+
+
+def mt(o, d, v0, e1, e2, tmin):
+    """orc_mt over n records (float32[n, 3] each, tmin float32[n]) -> (hit
+    uint8[n], t float32[n]; t = 0 on a miss)."""
+    L = lib()
+    L.orc_mt.restype = C.c_int
+    arrs = [_f32rows(x, 3) for x in (o, d, v0, e1, e2)]
+    tmin = np.ascontiguousarray(tmin, np.float32).reshape(-1)
+    n = tmin.size
+    hit, t = np.zeros(n, np.uint8), np.zeros(n, np.float32)
+    tt = C.c_float()
+    for i in range(n):
+        h = L.orc_mt(*[b + i * s for _, b, s in arrs], float(tmin[i]), C.byref(tt))
+        hit[i] = h
+        t[i] = tt.value if h else 0.0
+    return hit, t
+
+
+def slab(o, d, planes, tmin, tmax):
+    """orc_slab over n records (o, d float32[n, 3]; planes float32[n, 6] = lo.x,
+    hi.x, lo.y, hi.y, lo.z, hi.z) -> (hit uint8[n], tnear, tfar float32[n])."""
+    L = lib()
+    L.orc_slab.argtypes = [C.c_void_p] * 3 + [C.c_float, C.c_float, C.POINTER(C.c_float),
+                                              C.POINTER(C.c_float)]
+    L.orc_slab.restype = C.c_int
+    (_o, bo, so), (_d, bd, sd), (_p, bp, sp) = _f32rows(o, 3), _f32rows(d, 3), _f32rows(planes, 6)
+    tmin = np.ascontiguousarray(tmin, np.float32).reshape(-1)
+    tmax = np.ascontiguousarray(tmax, np.float32).reshape(-1)
+    n = tmin.size
+    hit, tn, tf = np.zeros(n, np.uint8), np.zeros(n, np.float32), np.zeros(n, np.float32)
+    a, b = C.c_float(), C.c_float()
+    for i in range(n):
+        hit[i] = L.orc_slab(bo + i * so, bd + i * sd, bp + i * sp, float(tmin[i]), float(tmax[i]),
+                            C.byref(a), C.byref(b))
+        tn[i], tf[i] = a.value, b.value
+    return hit, tn, tf
+
+
+def pcg_hash(v) -> np.ndarray:
+    L = lib()
+    L.orc_pcg_hash.argtypes = [C.c_uint32]
+    L.orc_pcg_hash.restype = C.c_uint32
+    return np.array([L.orc_pcg_hash(int(x)) for x in np.asarray(v, np.uint32).reshape(-1)], np.uint32)
+
+
+def pt_key(seed, px, v) -> np.ndarray:
+    L = lib()
+    L.orc_pt_key.argtypes = [C.c_uint32] * 3
+    L.orc_pt_key.restype = C.c_uint32
+    s, p, w = (np.asarray(x, np.uint32).reshape(-1) for x in (seed, px, v))
+    return np.array([L.orc_pt_key(int(a), int(b), int(c)) for a, b, c in zip(s, p, w)], np.uint32)
+
+
+def pt_u11(h) -> np.ndarray:
+    L = lib()
+    L.orc_pt_u11.argtypes = [C.c_uint32]
+    L.orc_pt_u11.restype = C.c_float
+    return np.array([L.orc_pt_u11(int(x)) for x in np.asarray(h, np.uint32).reshape(-1)], np.float32)
+
+
+def pt_bounce_dir(n, key) -> np.ndarray:
+    """orc_pt_bounce_dir over m records (n float32[m, 3], key uint32[m]) -> float32[m, 3]."""
+    L = lib()
+    L.orc_pt_bounce_dir.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
+    L.orc_pt_bounce_dir.restype = None
+    _n, bn, sn = _f32rows(n, 3)
+    key = np.asarray(key, np.uint32).reshape(-1)
+    out = np.zeros((key.size, 3), np.float32)
+    for i in range(key.size):
+        L.orc_pt_bounce_dir(bn + i * sn, int(key[i]), out.ctypes.data + 12 * i)
+    return out
+
+
+def pt_normal(e1, e2, din) -> np.ndarray:
+    """orc_pt_normal over m records (float32[m, 3] each) -> float32[m, 3]."""
+    L = lib()
+    L.orc_pt_normal.argtypes = [C.c_void_p] * 4
+    L.orc_pt_normal.restype = None
+    arrs = [_f32rows(x, 3) for x in (e1, e2, din)]
+    m = arrs[0][0].shape[0]
+    out = np.zeros((m, 3), np.float32)
+    for i in range(m):
+        L.orc_pt_normal(*[b + i * s for _, b, s in arrs], out.ctypes.data + 12 * i)
+    return out
+
+
+def trace_rays(tri9, rays, skip, tie_high, bvh=None, mode=0):
+    """orc_trace_rays: n rays (float32[n, 8]: o, d, tmin, tmax; skip int32[n];
+    tie_high bool[n]) over the triangles tri9 float32[P, 9] (v0, e1, e2 by pid).
+    mode 0: brute force; 1: the BVH2 of bvh = (nodes, tris[, nodes4]); 2: its
+    BVH4.  -> (pid int32[n], t float32[n] (0 on a miss), occluded uint8[n])."""
+    L = lib()
+    L.orc_trace_rays.argtypes = [C.POINTER(BvhC), C.c_void_p, C.c_int32, C.c_int, C.c_uint32] + [C.c_void_p] * 6
+    L.orc_trace_rays.restype = C.c_int
+    tri9 = np.ascontiguousarray(tri9, np.float32).reshape(-1, 9)
+    rays = np.ascontiguousarray(rays, np.float32).reshape(-1, 8)
+    skip = np.ascontiguousarray(skip, np.int32).reshape(-1)
+    tie = np.ascontiguousarray(tie_high, np.uint8).reshape(-1)
+    n = rays.shape[0]
+    assert skip.size == n and tie.size == n
+    pid, t, occ = np.zeros(n, np.int32), np.zeros(n, np.float32), np.zeros(n, np.uint8)
+    b, keep = None, None
+    if bvh is not None:
+        nodes = np.ascontiguousarray(bvh[0], np.float32)
+        tris = np.ascontiguousarray(bvh[1], np.float32)
+        bc = BvhC(nodes.shape[0], _ptr(nodes, C.c_float), tris.shape[0], _ptr(tris, C.c_float), 0, None)
+        keep = [nodes, tris]
+        if len(bvh) > 2 and bvh[2] is not None:
+            nodes4 = np.ascontiguousarray(bvh[2], np.float32)
+            bc.num_nodes4, bc.nodes4 = nodes4.shape[0], _ptr(nodes4, C.c_float)
+            keep.append(nodes4)
+        b = C.byref(bc)
+    rc = L.orc_trace_rays(b, tri9.ctypes.data, tri9.shape[0], mode, n, rays.ctypes.data, skip.ctypes.data,
+                          tie.ctypes.data, pid.ctypes.data, t.ctypes.data, occ.ctypes.data)
+    if rc != 0:
+        raise RuntimeError(f"orc_trace_rays failed: {rc}")
+    return pid, t, occ

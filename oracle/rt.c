@@ -185,19 +185,29 @@ static inline void ray_pre(ray_pre_t* r, const float o[3], const float d[3]) {
     r->oi[k] = o[k] * r->inv[k];
   }
 }
-/* slab test of child `ch` of a node; returns hit and tnear */
-static inline int slab(const float* n, int ch, const ray_pre_t* r, float tmin, float tmax, float* tnear) {
+/* slab test of one box (planes lo[k], hi[k]); returns hit, tnear and tfar --
+ * the one form every node step below uses (rt_trace.h slab / slab_nf) */
+static inline int slab_planes(const float plo[3], const float phi[3], const ray_pre_t* r, float tmin,
+                              float tmax, float* tnear, float* tfar) {
   float lo[3], hi[3];
   for (int k = 0; k < 3; ++k) {
-    lo[k] = fmaf(n[4 * k + 2 * ch + 0], r->inv[k], -r->oi[k]);
-    hi[k] = fmaf(n[4 * k + 2 * ch + 1], r->inv[k], -r->oi[k]);
+    lo[k] = fmaf(plo[k], r->inv[k], -r->oi[k]);
+    hi[k] = fmaf(phi[k], r->inv[k], -r->oi[k]);
   }
   const float t0 = fminf(lo[0], hi[0]), t1 = fminf(lo[1], hi[1]), t2 = fminf(lo[2], hi[2]);
   const float u0 = fmaxf(lo[0], hi[0]), u1 = fmaxf(lo[1], hi[1]), u2 = fmaxf(lo[2], hi[2]);
   const float tn = fmaxf(fmaxf(t0, t1), fmaxf(t2, tmin));
   const float tf = fminf(fminf(u0, u1), fminf(u2, tmax));
   *tnear = tn;
+  *tfar = tf;
   return tn <= tf;
+}
+/* slab test of child `ch` of a node; returns hit and tnear */
+static inline int slab(const float* n, int ch, const ray_pre_t* r, float tmin, float tmax, float* tnear) {
+  const float plo[3] = {n[2 * ch], n[4 + 2 * ch], n[8 + 2 * ch]};
+  const float phi[3] = {n[2 * ch + 1], n[4 + 2 * ch + 1], n[8 + 2 * ch + 1]};
+  float tf;
+  return slab_planes(plo, phi, r, tmin, tmax, tnear, &tf);
 }
 
 static inline int32_t node_ref(const float* n, int ch) {
@@ -220,16 +230,9 @@ static int32_t bvh4_step(const float* n, const ray_pre_t* r, float tmin, float l
   int cnt = 0;
   for (int i = 0; i < 4; ++i) {
     memcpy(&ref[i], &n[24 + i], 4);
-    float lo[3], hi[3];
-    for (int k = 0; k < 3; ++k) {
-      lo[k] = fmaf(n[8 * k + i], r->inv[k], -r->oi[k]);
-      hi[k] = fmaf(n[8 * k + 4 + i], r->inv[k], -r->oi[k]);
-    }
-    const float t0 = fminf(lo[0], hi[0]), t1 = fminf(lo[1], hi[1]), t2 = fminf(lo[2], hi[2]);
-    const float u0 = fmaxf(lo[0], hi[0]), u1 = fmaxf(lo[1], hi[1]), u2 = fmaxf(lo[2], hi[2]);
-    const float tn = fmaxf(fmaxf(t0, t1), fmaxf(t2, tmin));
-    const float tf = fminf(fminf(u0, u1), fminf(u2, lim));
-    const int h = ref[i] != BVH_EMPTY && tn <= tf;
+    const float plo[3] = {n[i], n[8 + i], n[16 + i]}, phi[3] = {n[4 + i], n[12 + i], n[20 + i]};
+    float tn, tf;
+    const int h = slab_planes(plo, phi, r, tmin, lim, &tn, &tf) && ref[i] != BVH_EMPTY;
     key[i] = h ? (anyhit ? (float)i : fminf(tn, FLT_MAX)) : INFINITY;
     cnt += h;
   }
@@ -763,6 +766,50 @@ static int trace_any(const rt_ctx_t* c, const float o[3], const float d[3], floa
                      float tmax, int anyhit, int skip, float* t, orc_rt_counters_t* k) {
   return c->bvh ? bvh_trace(c, o, d, tmin, tmax, anyhit, skip, t, &k->node_visits, &k->tri_tests)
                 : brute_trace(c, o, d, tmin, tmax, anyhit, skip, t, &k->tri_tests);
+}
+
+/* ---- the ray routines as tables (unit tests: tests/test_ray_kat_cpu.py) -- */
+int orc_slab(const float o[3], const float d[3], const float planes[6], float tmin, float tmax,
+             float* tnear, float* tfar) {
+  ray_pre_t rp;
+  ray_pre(&rp, o, d);
+  const float plo[3] = {planes[0], planes[2], planes[4]}, phi[3] = {planes[1], planes[3], planes[5]};
+  return slab_planes(plo, phi, &rp, tmin, tmax, tnear, tfar);
+}
+uint32_t orc_pcg_hash(uint32_t v) { return pcg_hash(v); }
+uint32_t orc_pt_key(uint32_t seed, uint32_t px, uint32_t v) { return pt_key(seed, px, v); }
+float orc_pt_u11(uint32_t h) { return pt_u11(h); }
+void orc_pt_bounce_dir(const float n[3], uint32_t key, float dir[3]) { pt_bounce_dir(n, key, dir); }
+void orc_pt_normal(const float e1[3], const float e2[3], const float din[3], float n[3]) {
+  float tri[9] = {0.0f, 0.0f, 0.0f, e1[0], e1[1], e1[2], e2[0], e2[1], e2[2]};
+  pt_normal(tri, din, n);
+}
+int orc_trace_rays(const orc_bvh_t* bvh, const float* tri9, int32_t num_prims, int mode, uint32_t n,
+                   const float* rays, const int32_t* skip, const uint8_t* tie_high, int32_t* pid,
+                   float* t, uint8_t* occluded) {
+  if (mode < 0 || mode > 2 || (mode != 0 && !bvh) || (mode == 2 && bvh->num_nodes4 <= 0)) return -1;
+  rt_ctx_t* c = (rt_ctx_t*)calloc(1, sizeof(rt_ctx_t));
+  orc_bvh_t b;
+  if (bvh) b = *bvh;
+  if (mode == 1) b.num_nodes4 = 0;
+  c->bvh = mode ? &b : NULL;
+  c->tri = (float*)tri9;
+  c->num_geom = num_prims;
+  c->geom = (int32_t*)malloc(sizeof(int32_t) * (size_t)(num_prims > 0 ? num_prims : 1));
+  for (int i = 0; i < num_prims; ++i) c->geom[i] = i;
+  orc_rt_counters_t k;
+  memset(&k, 0, sizeof(k));
+  for (uint32_t i = 0; i < n; ++i) {
+    const float* r = rays + (size_t)i * 8;
+    c->tie_high = tie_high[i] != 0;
+    float tc = 0.0f, ta = 0.0f;
+    pid[i] = trace_any(c, r, r + 3, r[6], r[7], 0, skip[i], &tc, &k);
+    t[i] = pid[i] >= 0 ? tc : 0.0f;
+    occluded[i] = trace_any(c, r, r + 3, r[6], r[7], 1, skip[i], &ta, &k) >= 0;
+  }
+  free(c->geom);
+  free(c);
+  return 0;
 }
 
 static int sl_occluded(const rt_ctx_t* c, const float so[3], const float sd[3], int skip,

@@ -52,6 +52,7 @@
 #define PT_PAIR 0
 #endif
 #include "rt_trace.h"
+#include "rt_path.h"  // pcg_hash, pt_key, pt_u11, bounce_dir, tri_normal
 
 // PT_MODE 1 (default image pt_kernel): every lane runs its own path to the
 // end in registers (one-wave workgroups, no queue): divergent, but waves
@@ -70,42 +71,12 @@
 #define PT_PAIR 1        // 0: no paired-vertex code (the shadow lists never pair)
 #endif
 #define PT_SKY 0.25f     // radiance of an escaped bounce ray (oracle ORC_PT_SKY)
-#define PT_TRIES 8u      // disk rejection-sampling attempts (ORC_PT_TRIES)
 
 namespace {
 
 using namespace rtk;
 
 constexpr int kWaves = PT_BLOCK / 64;
-
-__device__ __forceinline__ uint32_t pcg_hash(uint32_t v) {
-  const uint32_t state = v * 747796405u + 2891336453u;
-  const uint32_t word = ((state >> ((state >> 28u) + 4u)) ^ state) * 277803737u;
-  return (word >> 22u) ^ word;
-}
-__device__ __forceinline__ uint32_t pt_key(uint32_t seed, uint32_t px, uint32_t v) {
-  return pcg_hash(px ^ pcg_hash(seed ^ (0x9E3779B9u * (v + 1u))));
-}
-__device__ __forceinline__ float pt_u11(uint32_t h) {
-  return (float)(h >> 8) * 0x1p-23f - 1.0f;
-}
-
-// cosine-weighted direction about unit normal n (oracle pt_bounce_dir)
-__device__ __forceinline__ void bounce_dir(const float n[3], uint32_t key, float dir[3]) {
-  float x = 0.0f, y = 0.0f;
-  for (uint32_t i = 0; i < PT_TRIES; ++i) {
-    const float a = pt_u11(pcg_hash(key + 2u * i)), b = pt_u11(pcg_hash(key + 2u * i + 1u));
-    if (fmaf(a, a, b * b) < 1.0f) { x = a; y = b; break; }
-  }
-  const float z = sqrtf(1.0f - fmaf(x, x, y * y));
-  const float sgn = n[2] >= 0.0f ? 1.0f : -1.0f;
-  const float a = -1.0f / (sgn + n[2]);
-  const float b = (n[0] * n[1]) * a;
-  const float t1[3] = {fmaf(sgn * (n[0] * n[0]), a, 1.0f), sgn * b, -(sgn * n[0])};
-  const float t2[3] = {b, fmaf(n[1] * n[1], a, sgn), -n[1]};
-#pragma unroll
-  for (int k = 0; k < 3; ++k) dir[k] = fmaf(x, t1[k], fmaf(y, t2[k], z * n[k]));
-}
 
 __device__ __forceinline__ void load_tri(const Scene& S, int32_t pid, float v0[3], float e1[3],
                                          float e2[3]) {
@@ -114,15 +85,6 @@ __device__ __forceinline__ void load_tri(const Scene& S, int32_t pid, float v0[3
   v0[0] = a.x; v0[1] = a.y; v0[2] = a.z;
   e1[0] = b.x; e1[1] = b.y; e1[2] = b.z;
   e2[0] = c.x; e2[1] = c.y; e2[2] = c.z;
-}
-
-// unit geometric normal facing against din (oracle pt_normal)
-__device__ __forceinline__ void tri_normal(const float e1[3], const float e2[3], const float din[3],
-                                           float n[3]) {
-  cross3(n, e1, e2);
-  const float len = sqrtf(dot3(n, n));
-  n[0] = n[0] / len; n[1] = n[1] / len; n[2] = n[2] / len;
-  if (dot3(n, din) > 0.0f) { n[0] = -n[0]; n[1] = -n[1]; n[2] = -n[2]; }
 }
 
 // MT barycentrics of vertex 1 and 2 (oracle mt_bary)
