@@ -605,6 +605,99 @@ int rt_read_relight_base(rt_renderer_h r, uint32_t* out, uint64_t count);
 uint32_t rt_relight_resolve(uint32_t base_argb, uint32_t depth_flags, uint32_t light_mask, const uint8_t* weights,
                             uint32_t n);
 
+/* Denoising accumulated path frames on the device, guided by visibility.  NO
+ * REFERENCE (the reference has no path tracer; the filter is defined here in
+ * integer arithmetic and held bit for bit to a numpy restatement of this text,
+ * tests/denoise_reference.py).
+ *
+ * An edge-avoiding a-trous filter over the accumulation records: the mean
+ * radiance is demodulated by the primary albedo, filtered over P passes of a
+ * 5 x 5 B3-spline kernel at strides 1, 2, 4, 8, 16 under four edge stops
+ * (primitive, depth, geometric normal, irradiance), remodulated and stored to
+ * the framebuffer in use.  The records are only read: accumulation goes on.
+ *
+ * Per pixel p.  Inputs: the accumulation record {s_R, s_G, s_B, n}, n >= 1;
+ * the guide pid, z (the 24-bit depth word) and geom (RT_AOV_GEOM), exactly
+ * rt_aov_t's pid and depth_flags of the primary+shadow configuration of the
+ * same scene and size; the base colour A (ARGB: the pixel shaded without
+ * shadows, the path's starting throughput); the guide normal N, three signed
+ * bytes.
+ *   Normal: e1, e2 of pid's RT_REC_PTRIS record; n = cross(e1, e2), len =
+ *   sqrtf(dot(n, n)), n / len in binary32 (kernels/rt_path.h tri_normal's first
+ *   three statements, no facing flip); N_i = (int)rintf(n_i * 127.0f); N = 0
+ *   when len is 0 or not finite.  0 for a pixel without geom.
+ *   Demodulate (geom pixels), per channel c: d = n * max(A_c, 1), I_c =
+ *   min(65535, (256 * s_c + d / 2) / d) in integer division (64 bits).
+ *   Pass k = 1..P, stride st = 2^(k-1), geom pixels: taps q = p + st * (i, j),
+ *   i, j in -2..2, inside the image and with geom(q); h(i, j) = b_i * b_j, b =
+ *   (1, 4, 6, 4, 1); w(p, p) = 256, else w = (wz * wn * wl) >> 16 with
+ *     pid_q == pid_p: wz = wn = 256; otherwise
+ *     wz = E(|z_p - z_q| >> (zs + k - 1)),
+ *     c = min(256, |N_p . N_q| >> 6), wn = (c * c) >> 8, then wn = (wn * wn) >> 8;
+ *     wl = E(max_c |I_c(p) - I_c(q)| >> ls) on the pass's input;
+ *     E(e) = e >= 9 ? 0 : 256 >> e.
+ *   I'_c(p) = (sum h * w * I_c(q) + den / 2) / den, den = sum h * w.  Every sum
+ *   fits 32 bits: 256 * 256 * 65535 + 32768 < 2^32.
+ *   Store.  A geom pixel: alpha(A) | min(255, (I_c * A_c + 128) >> 8) per
+ *   channel; any other pixel: rt_accum_resolve(record, A).
+ * Parameters: passes 1..5; depth_shift zs 0..23; color_shift ls 0..16 (16: no
+ * irradiance difference reaches 2^16, the irradiance stop is off).
+ * RT_DENOISE_DEFAULT_* is what tests/test_gpu_denoise.py's error test runs.
+ *
+ * rt_denoise_capture_start: one launch (image rt_aov_guide: kernels/
+ * rt_aov_kernel.hip built with RT_AOV_BASE=2) writing, per framebuffer pixel,
+ * the guide record and the base colour into buffers of its own; it writes
+ * neither the framebuffer nor an accumulation record.  Valid on a
+ * configuration rt_renderer_accum_begin accepts (before or after that call)
+ * with a linear framebuffer: -2 (rt_last_error says why) for everything
+ * rt_renderer_accum_begin refuses, for RT_RENDER_COMPACT or shards, for a
+ * scene with a non-empty ordered tail.  (rt_render_aov_start stays refused on
+ * path frames.)  The guide depends on view and resolution only: it survives
+ * rt_renderer_set_light, rt_renderer_set_path_lights, rt_renderer_accum_reset
+ * and further accumulation; rt_renderer_configure and rt_renderer_free release
+ * it.  An ordinary launch as a record launch is (no lane, behind the frames
+ * in flight on both lanes).  The three images (the kernel directory's, else
+ * the library's) are loaded by the first call and kept.
+ *
+ * rt_render_denoise_start: -2 without a capture since the last configure,
+ * without an accumulated sample (rt_renderer_accum_samples = 0), or with a
+ * parameter out of range.  It queues 1 + passes ordinary launches with no host
+ * wait and no copy -- prepare (rt_denoise_prep: demodulate, pack the taps'
+ * records), then the passes (rt_denoise_pass), the last of which remodulates
+ * and stores -- no launch lane, behind the frames in flight on both lanes;
+ * the parameters travel in launch words and tag.  It writes the framebuffer in
+ * use, as a relight launch does: rt_read_framebuffer returns the denoised
+ * frame, rt_render_wait covers it, rt_render_kernel_ms describes its last
+ * launch.  Frames of several path lights are admitted: records and the sample
+ * cursor keep their form. */
+typedef struct {
+  int32_t  pid;          /* rt_aov_t::pid */
+  uint32_t depth_flags;  /* rt_aov_t::depth_flags without RT_AOV_SHADOW_RAY: the depth word, RT_AOV_GEOM */
+  uint32_t normal;       /* N: signed bytes x | y << 8 | z << 16 (bits 24-31 zero) */
+  uint32_t reserved;     /* 0 */
+} rt_denoise_guide_t;
+typedef struct {
+  uint32_t passes;       /* 1..5 */
+  uint32_t depth_shift;  /* zs, 0..23 */
+  uint32_t color_shift;  /* ls, 0..16 */
+} rt_denoise_params_t;
+#define RT_DENOISE_DEFAULT_PASSES 2u
+#define RT_DENOISE_DEFAULT_DEPTH_SHIFT 2u
+#define RT_DENOISE_DEFAULT_COLOR_SHIFT 3u
+int rt_denoise_capture_start(rt_renderer_h r);
+int rt_denoise_capture(rt_renderer_h r);    /* start + wait */
+int rt_render_denoise_start(rt_renderer_h r, const rt_denoise_params_t* params);
+int rt_render_denoise(rt_renderer_h r, const rt_denoise_params_t* params);  /* start + wait */
+/* the capture's guide records and base colours in framebuffer order (either may be NULL), count >=
+ * the framebuffer's pixels (waits for the device).  NO REFERENCE. */
+int rt_read_denoise_guide(rt_renderer_h r, rt_denoise_guide_t* guide, uint32_t* base, uint64_t count);
+/* Restore an accumulation, for checkpoint and resume: rec = uint32[count][4] in framebuffer order
+ * as rt_read_accum returns them, count >= the framebuffer's pixels; every record's n must equal
+ * `n` in 1..2^24, else -2.  Sets the sample cursor to n: the next accumulation launch continues
+ * with sample n and does not reset.  After rt_renderer_accum_begin only; waits for the device.
+ * NO REFERENCE. */
+int rt_write_accum(rt_renderer_h r, const uint32_t* rec, uint64_t count, uint32_t n);
+
 /* Read back one per-resolution record array of the current configuration
  * (layouts: kernels/rt_common.h; NO REFERENCE).  out NULL = size query
  * (*size = bytes). */

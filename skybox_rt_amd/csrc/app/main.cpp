@@ -26,7 +26,12 @@
 // same: its head traced, its ordered tail folded through the output merger,
 // vx_rt.h); -A samples, with -P: that many samples per pixel accumulated on
 // the device (rt_render_accumulate: launches of 32, then one for the rest)
-// and their mean written, -r comparing as usual; -V file: after the frame one
+// and their mean written, -r comparing as usual; -D passes[,zs,ls], with -A:
+// after the samples a guide capture (rt_denoise_capture) and the edge-avoiding
+// filter over the records (rt_render_denoise: passes 1..5, depth shift zs and
+// irradiance shift ls, by default RT_DENOISE_DEFAULT_*), whose frame is the one
+// written to -o, and one line "Denoise: <passes> passes, zs <zs>, ls <ls>, capture <ms> ms, filter <ms> ms host wall";
+// -V file: after the frame one
 // visibility-record launch (rt_render_aov) of the same configuration and
 // lights, written as a 16-byte header ('RTAV', width, height, 16) and the
 // rt_aov_t records in framebuffer order (with -G: this rank's compact tiles),
@@ -86,6 +91,7 @@ uint32_t accum_samples = 0;           // -A: with -P, accumulate this many sampl
 std::vector<std::array<float, 3>> more_lights;  // -M: lights beside the one of -L
 const char* aov_file = nullptr;       // -V: write the frame's visibility records
 const char* weights_arg = nullptr;    // -W: relight the frame under these per-light weights
+const char* denoise_arg = nullptr;    // -D: with -A, denoise the accumulated frame
 
 #ifdef RT_APP_RASTER
 const char* kOpts = "t:i:o:r:w:h:k:n:z?";
@@ -95,7 +101,7 @@ void usage() {
               "[-k tilelogsize] [-n repeat]\n");
 }
 #else
-const char* kOpts = "t:s:e:i:o:r:w:h:k:n:L:M:P:G:I:B:A:V:W:uxyzSRFHO?";
+const char* kOpts = "t:s:e:i:o:r:w:h:k:n:L:M:P:G:I:B:A:V:W:D:uxyzSRFHO?";
 void usage() {
   std::printf("Vortex 3D Rendering Test (MI355X).\n"
               "Usage: [-t trace] [-s startdraw] [-e enddraw] [-o output] [-r reference] [-w width] "
@@ -105,6 +111,7 @@ void usage() {
               "       [-O trace the head, fold blended / stencil / masked drawcalls (RT_SCENE_OM_LAYERS)]\n"
               "       [-A samples: with -P, accumulate that many samples per pixel on the device and "
               "write their mean]\n"
+              "       [-D passes[,zs,ls]: with -A, write the accumulated frame through the edge-avoiding filter]\n"
               "       [-V file: the frame's per-pixel visibility records (primary + shadow frames)]\n"
               "       [-W w0,w1,...: with -S, relight the frame under one weight 0..255 per light of -L / -M]\n"
               "       env RT_KERNEL_DIR: kernel images; RT_ASSETS_PATHS: search directories\n");
@@ -156,6 +163,7 @@ int main(int argc, char** argv) {
     case 'A': accum_samples = (uint32_t)std::atoi(optarg); break;
     case 'V': aov_file = optarg; break;
     case 'W': weights_arg = optarg; break;
+    case 'D': denoise_arg = optarg; break;
 #endif
     case '?': usage(); return 0;
     default: usage(); return -1;  // -i: in the reference's option string, never handled
@@ -191,6 +199,16 @@ int main(int argc, char** argv) {
   if (accum_samples && (bounces < 0 || rank >= 0)) {
     std::printf("Error: -A samples needs -P bounces (path tracing), one rank\n");
     return 1;
+  }
+  rt_denoise_params_t dn = {RT_DENOISE_DEFAULT_PASSES, RT_DENOISE_DEFAULT_DEPTH_SHIFT,
+                            RT_DENOISE_DEFAULT_COLOR_SHIFT};
+  if (denoise_arg) {
+    const int got = std::sscanf(denoise_arg, "%u,%u,%u", &dn.passes, &dn.depth_shift, &dn.color_shift);
+    if (!accum_samples || (got != 1 && got != 3)) {
+      std::printf("Error: -D passes[,zs,ls] needs -P bounces -A samples\n");
+      usage();
+      return 1;
+    }
   }
   std::vector<uint8_t> weights;
   if (weights_arg) {
@@ -341,6 +359,17 @@ int main(int argc, char** argv) {
     std::printf("Accumulated %u samples per pixel in %u launches, %.4f ms in all\n", accum_samples, launches,
                 total);
     repeat = 1;  // the line below: the time of all launches, the rays of all samples
+    if (denoise_arg) {
+      // the guide, then prepare + passes into the framebuffer in use; the sum of the launches' times
+      RT_CHECK(rt_denoise_capture(r));
+      double ms = 0.0, dms = 0.0;
+      RT_CHECK(rt_render_kernel_ms(r, &ms));
+      const auto t0 = std::chrono::steady_clock::now();
+      RT_CHECK(rt_render_denoise(r, &dn));
+      dms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+      std::printf("Denoise: %u passes, zs %u, ls %u, capture %.4f ms, filter %.4f ms host wall\n", dn.passes,
+                  dn.depth_shift, dn.color_shift, ms, dms);
+    }
   }
   for (uint32_t i = 0; !accum_samples && i < repeat; ++i) {
     RT_CHECK(rt_render(r));

@@ -1277,6 +1277,10 @@ int rt_renderer_configure(rt_renderer_h r, const rt_render_params_t* p) {
   if (release_idle(r, &r->relight_base) != 0) return -1;
   r->relight_base_bytes = 0;
   r->relight_n = 0;
+  // and the denoiser's guide, base colours and tap buffers; its capture is over
+  if (release_idle(r, &r->dn_buf) != 0) return -1;
+  r->dn_bytes = 0;
+  r->dn_captured = false;
   r->nlights = 0;  // a configure returns to one light (rt_renderer_set_lights)
   rt_kernel_arg_t& a = r->arg;
   a.width = p->width;
@@ -1502,8 +1506,9 @@ int rt_renderer_configure(rt_renderer_h r, const rt_render_params_t* p) {
   // (and the light table of rt_renderer_set_lights)
   // (and the visibility records' area: rt_render_aov_start writes it)
   // (and the relight area: rt_relight_capture_start writes it)
+  // (and the denoiser's area: rt_denoise_capture_start writes it)
   if (!r->args &&
-      upload(r->dev, nullptr, RT_RELIGHT_ARG_OFFSET + sizeof(rt_relight_arg_t), &r->args, &args_addr))
+      upload(r->dev, nullptr, RT_DENOISE_ARG_OFFSET + sizeof(rt_denoise_arg_t), &r->args, &args_addr))
     return -1;
   if (rtapp::write_args(r, 0, &a, sizeof(a)) != 0)
     return fail("render argument upload failed");
@@ -1663,21 +1668,28 @@ int rt_render(rt_renderer_h r) {
 
 // ---- progressive accumulation (vx_rt.h; NO REFERENCE) ---------------------
 
-int rt_renderer_accum_begin(rt_renderer_h r) {
-  if (!r || !r->configured) return fail("renderer not configured");
+// what rt_renderer_accum_begin admits (`who`: that call, or rt_denoise_capture, which is valid
+// on the same configurations)
+static int accum_admit(rt_renderer_h r, const char* who_c) {
+  const std::string who = who_c;
   const uint32_t f = r->params.flags;
-  if (!(f & RT_RENDER_PATH)) return fail("rt_renderer_accum_begin: not an RT_RENDER_PATH configuration", -2);
+  if (!(f & RT_RENDER_PATH)) return fail(who + ": not an RT_RENDER_PATH configuration", -2);
   if (f & RT_RENDER_INSTRUMENTED)
-    return fail("rt_renderer_accum_begin: no instrumented accumulation image (RT_RENDER_INSTRUMENTED)", -2);
-  if (r->pq) return fail("rt_renderer_accum_begin: the two-kernel path queue (RT_PT_QUEUE=1) does not accumulate", -2);
+    return fail(who + ": no instrumented accumulation image (RT_RENDER_INSTRUMENTED)", -2);
+  if (r->pq) return fail(who + ": the two-kernel path queue (RT_PT_QUEUE=1) does not accumulate", -2);
   // (a scene without geometry starts no path and walks no tree: any image serves it)
   if (r->arg.num_geom > 0 && r->generic_tree())
-    return fail("rt_renderer_accum_begin: pt_accum walks the binary16 BVH4 only; this tree runs the generic "
+    return fail(who + ": pt_accum walks the binary16 BVH4 only; this tree runs the generic "
                 "(deep) images", -2);
-  if (!r->set_words) return fail("rt_renderer_accum_begin: the driver passes no launch words", -2);
+  if (!r->set_words) return fail(who + ": the driver passes no launch words", -2);
   // (next to the pt_kernel.vxbin in use: a directory with a path tracer of its own and no
   // pt_accum, e.g. pt_compact, is refused)
-  if (const int e = rtapp::load_images(r, rtimg::GRP_ACCUM, "rt_renderer_accum_begin")) return e;
+  return rtapp::load_images(r, rtimg::GRP_ACCUM, who_c);
+}
+
+int rt_renderer_accum_begin(rt_renderer_h r) {
+  if (!r || !r->configured) return fail("renderer not configured");
+  if (const int e = accum_admit(r, "rt_renderer_accum_begin")) return e;
   const uint64_t bytes = r->cbuf_bytes * 4;  // 16 B per framebuffer pixel
   if (!r->accum || r->accum_bytes != bytes) {
     // (upload frees the old buffer: not under launches still writing it)
@@ -1935,6 +1947,129 @@ uint32_t rt_relight_resolve(uint32_t base_argb, uint32_t depth_flags, uint32_t l
   if (W == 0) return base_argb;
   const rt_relight_div_t d = rt_relight_div(W);
   return rt_relight_mix(base_argb, rt_relight_occluded(light_mask, w, n), W, d.s, d.m);
+}
+
+// ---- denoising accumulated path frames (vx_rt.h; NO REFERENCE) -------------
+
+static_assert(sizeof(rt_denoise_guide_t) == 16, "one 16-byte guide record per pixel");
+
+int rt_denoise_capture_start(rt_renderer_h r) {
+  if (!r || !r->configured) return fail("renderer not configured");
+  if (const int e = accum_admit(r, "rt_denoise_capture")) return e;
+  if ((r->arg.flags & RT_FLAG_COMPACT) || r->params.shard_count > 1)
+    return fail("rt_denoise_capture: a linear framebuffer only (the filter's taps are image neighbours; compact "
+                "and sharded output keep tiles, not rows)", -2);
+  if (!r->sc->tail_prims.empty())
+    return fail("rt_denoise_capture: a scene with an ordered tail has no guide (its tail's fragments are merged, "
+                "not traced)", -2);
+  if (!r->set_tag) return fail("rt_denoise_capture: the driver passes no launch tag (the passes' parameters)", -2);
+  if (aov_image(r, "rt_aov_guide.vxbin", &r->dn_guide_img) != 0 ||
+      aov_image(r, "rt_denoise_prep.vxbin", &r->dn_prep_img) != 0 ||
+      aov_image(r, "rt_denoise_pass.vxbin", &r->dn_pass_img) != 0)
+    return -1;
+  const uint64_t npix = r->cbuf_bytes / 4, bytes = npix * 44;
+  if (!r->dn_buf || r->dn_bytes != bytes) {
+    // (upload frees the old buffer: not under launches still writing it)
+    if (r->dn_buf && vx_ready_wait(r->dev, VX_MAX_TIMEOUT) != 0) return fail("vx_ready_wait failed");
+    r->dn_captured = false;
+    r->dn_bytes = 0;
+    uint64_t addr = 0;
+    if (upload(r->dev, nullptr, bytes, &r->dn_buf, &addr)) return -1;
+    r->dn_bytes = bytes;
+    // guide 16 B, tap guide 8 B, irradiance 8 B + 8 B, base colour 4 B per pixel: every part at a
+    // multiple of its entry size past the buffer's (256-B aligned) start
+    rt_denoise_arg_t da{};
+    da.guide_addr = addr;
+    da.tapg_addr = addr + 16 * npix;
+    da.irr_addr[0] = addr + 24 * npix;
+    da.irr_addr[1] = addr + 32 * npix;
+    da.base_addr = addr + 40 * npix;
+    da.width = r->arg.width;
+    da.height = r->arg.height;
+    da.cbuf1_off = r->cbuf1_off;
+    // behind the launches in flight (they read the areas in front), ahead of every launch started after it
+    if (rtapp::write_args(r, RT_DENOISE_ARG_OFFSET, &da, sizeof(da)) != 0)
+      return fail("denoise argument upload failed");
+  }
+  // The guide depends on view and resolution only: no light reaches the launch (its words are
+  // zero, it traces no shadow ray).  An ordinary launch on the image's own grid, as a record
+  // launch is: behind the frames in flight on both lanes, ahead of what starts after it.
+  const uint32_t lw[4] = {0, 0, 0, 0};
+  if (r->set_counters && r->set_counters(r->dev, (r->params.flags & RT_RENDER_COUNTERS) ? 1 : 0) != 0)
+    return fail("vx_hip_set_counters failed");
+  if (r->set_words(r->dev, lw, 4) != 0) return fail("vx_hip_set_launch_words failed");
+  if (vx_start(r->dev, r->dn_guide_img, r->args) != 0) return fail("vx_start failed");
+  r->dn_captured = true;
+  return 0;
+}
+
+int rt_denoise_capture(rt_renderer_h r) {
+  const int e = rt_denoise_capture_start(r);
+  return e ? e : rt_render_wait(r);
+}
+
+int rt_render_denoise_start(rt_renderer_h r, const rt_denoise_params_t* p) {
+  if (!r || !r->configured) return fail("renderer not configured");
+  if (!p) return fail("null argument");
+  if (!r->dn_captured || !r->dn_buf)
+    return fail("rt_render_denoise: no capture since the last configure (rt_denoise_capture)", -2);
+  if (!r->accum_on || r->accum_n == 0)
+    return fail("rt_render_denoise: no accumulated sample (rt_renderer_accum_begin, rt_render_accumulate)", -2);
+  if (p->passes < 1 || p->passes > RT_DN_MAX_PASSES) return fail("rt_render_denoise: passes must be in [1, 5]", -2);
+  if (p->depth_shift > RT_DN_MAX_ZS) return fail("rt_render_denoise: depth_shift must be in [0, 23]", -2);
+  if (p->color_shift > RT_DN_MAX_LS) return fail("rt_render_denoise: color_shift must be in [0, 16]", -2);
+  // into the framebuffer in use, as a relight launch goes: no flip, no lane
+  const int buf = r->cur_buf < 0 ? 0 : r->cur_buf;
+  const uint32_t lw[4] = {p->depth_shift, p->color_shift, 0, 0};
+  // (the launches count nothing: no counter rows)
+  if (r->set_counters && r->set_counters(r->dev, 0) != 0) return fail("vx_hip_set_counters failed");
+  // prepare, then the passes: ordinary launches in stream order, each reading what the one before wrote
+  if (r->set_words(r->dev, lw, 4) != 0) return fail("vx_hip_set_launch_words failed");
+  if (r->set_tag(r->dev, 0) != 0) return fail("vx_hip_set_launch_tag failed");
+  if (vx_start(r->dev, r->dn_prep_img, r->args) != 0) return fail("vx_start failed");
+  for (uint32_t k = 1; k <= p->passes; ++k) {
+    const uint32_t tag = k | (k == p->passes ? RT_DN_TAG_LAST : 0u) | (buf ? RT_DN_TAG_CBUF1 : 0u);
+    if (r->set_words(r->dev, lw, 4) != 0) return fail("vx_hip_set_launch_words failed");
+    if (r->set_tag(r->dev, tag) != 0) return fail("vx_hip_set_launch_tag failed");
+    if (vx_start(r->dev, r->dn_pass_img, r->args) != 0) return fail("vx_start failed");
+  }
+  r->prev_buf = -1;
+  r->cur_buf = buf;
+  return 0;
+}
+
+int rt_render_denoise(rt_renderer_h r, const rt_denoise_params_t* p) {
+  const int e = rt_render_denoise_start(r, p);
+  return e ? e : rt_render_wait(r);
+}
+
+int rt_read_denoise_guide(rt_renderer_h r, rt_denoise_guide_t* guide, uint32_t* base, uint64_t count) {
+  if (!r || !r->configured) return fail("renderer not configured");
+  if (!guide && !base) return fail("null argument");
+  if (!r->dn_captured || !r->dn_buf) return fail("rt_read_denoise_guide: no capture (rt_denoise_capture)", -2);
+  const uint64_t npix = r->cbuf_bytes / 4;
+  if (count < npix) return fail("buffer too small");
+  if (guide && vx_copy_from_dev(guide, r->dn_buf, 0, 16 * npix) != 0) return fail("vx_copy_from_dev failed");
+  if (base && vx_copy_from_dev(base, r->dn_buf, 40 * npix, 4 * npix) != 0) return fail("vx_copy_from_dev failed");
+  return 0;
+}
+
+int rt_write_accum(rt_renderer_h r, const uint32_t* rec, uint64_t count, uint32_t n) {
+  if (!r || !rec || !r->configured) return fail("renderer not configured");
+  if (!r->accum_on) return fail("rt_write_accum: no accumulation begun (rt_renderer_accum_begin)", -2);
+  if (n < 1 || n > RT_ACCUM_MAX_SAMPLES) return fail("rt_write_accum: n must be in [1, 2^24]", -2);
+  if (count * 16 < r->accum_bytes) return fail("buffer too small");
+  const uint64_t npix = r->accum_bytes / 16;
+  for (uint64_t i = 0; i < npix; ++i)
+    if (rec[4 * i + 3] != n)
+      return fail("rt_write_accum: record " + std::to_string(i) + " holds " + std::to_string(rec[4 * i + 3]) +
+                  " samples, not " + std::to_string(n), -2);
+  // (not under launches still reading or writing the records)
+  if (vx_ready_wait(r->dev, VX_MAX_TIMEOUT) != 0) return fail("vx_ready_wait failed");
+  if (vx_copy_to_dev(r->accum, rec, 0, r->accum_bytes) != 0) return fail("vx_copy_to_dev failed");
+  r->accum_n = n;          // the sample cursor: the next launch traces samples n ..
+  r->accum_reset = false;  // and reads the records
+  return 0;
 }
 
 int rt_render_stats(rt_renderer_h r, rt_stats_t* st) {

@@ -130,6 +130,15 @@ struct rt_renderer {
   vx_buffer_h aov_base_img = nullptr, relight_img = nullptr, relight_base = nullptr;
   uint64_t relight_base_bytes = 0;
   uint32_t relight_n = 0;
+  // denoising (vx_rt.h rt_denoise_capture_start / rt_render_denoise_start): the rt_aov_guide,
+  // rt_denoise_prep and rt_denoise_pass images, loaded and kept the same way, and one buffer of the
+  // current configuration holding, per framebuffer pixel, the guide record (16 B), the tap guide
+  // (8 B), the two irradiance buffers (8 B each) and the base colour (4 B), in that order
+  // (rt_common.h rt_denoise_arg_t names each part).  dn_captured: a capture was queued since the
+  // last configure
+  vx_buffer_h dn_guide_img = nullptr, dn_prep_img = nullptr, dn_pass_img = nullptr, dn_buf = nullptr;
+  uint64_t dn_bytes = 0;
+  bool dn_captured = false;
   vx_buffer_h nodes = nullptr, nodes4 = nullptr, tris = nullptr, layers = nullptr, dcs = nullptr, tex = nullptr;
   vx_buffer_h ptris = nullptr, geom = nullptr, oms = nullptr, bbox = nullptr, zbuf = nullptr;
   vx_buffer_h order = nullptr;
@@ -242,7 +251,8 @@ struct rt_renderer {
                            &order, &vnodes, &vtris, &vlayers, &vgeom, &gather_recv, &gather_image, &prims,
                            &cbuf, &cbuf1, &args, &verts, &pdc, &dcz, &layer_list, &geometry_list, &vis,
                            &blist, &bidx, &cdesc, &bglayer, &sidx, &slist, &pathq, &pathq_ctr, &oidx, &olist, &ovtris,
-                           &accum, &aov, &aov_img, &relight_base, &aov_base_img, &relight_img};
+                           &accum, &aov, &aov_img, &relight_base, &aov_base_img, &relight_img,
+                           &dn_guide_img, &dn_prep_img, &dn_pass_img, &dn_buf};
     for (auto* b : bufs) {
       if (*b) vx_mem_free(*b);
       *b = nullptr;

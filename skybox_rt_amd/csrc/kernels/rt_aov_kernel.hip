@@ -29,6 +29,18 @@
 // as rt_kernel calls it, the colour a frame of this configuration without
 // RT_RENDER_SHADOWS stores -- written at the pixel's framebuffer index into the
 // base-colour buffer (rt_common.h rt_relight_arg_t), for rt_relight_kernel.hip.
+//
+// Image rt_aov_guide (RT_AOV_BASE=2; vx_rt.h rt_denoise_capture_start): the
+// denoiser's capture, launched under a path configuration's arguments -- the
+// task map is the one pt_kernel deals its waves by (chunk_map / chunk_pixel:
+// 32-pixel waves of split tiles leave their upper lanes off the image), and
+// primary visibility, layers and shade_wave are what pt_kernel runs before it
+// starts a path.  Per pixel the guide record {pid, depth word | RT_AOV_GEOM,
+// geometric normal, 0} (rt_common.h rt_denoise_arg_t) in place of the
+// visibility record, and the base colour; no shadow ray is traced.  A third
+// build and not a launch of rt_aov_base: that image would trace one shadow ray
+// per pixel for a mask nobody reads, and the normal would need a pass of its
+// own over pid and the triangle records -- here the lane has the pid in hand.
 #include <hip/hip_runtime.h>
 
 #ifndef RT_BLOCK_THREADS
@@ -48,18 +60,46 @@ namespace {
 
 using namespace rtk;
 
+#if RT_AOV_BASE != 2
 // the record buffer as an arena offset (rt_app checks it lies below 4 GiB)
 __device__ __forceinline__ uint32_t aov_base(const Scene& S) {
   return (uint32_t)arg_at<rt_aov_arg_t>(S, RT_AOV_ARG_OFFSET)->aov_addr;
 }
+#endif
 
-#if RT_AOV_BASE
+#if RT_AOV_BASE == 2
+// the guide records and the base colours of the denoiser's capture, the same way
+__device__ __forceinline__ uint32_t guide_records(const Scene& S) {
+  return (uint32_t)arg_at<rt_denoise_arg_t>(S, RT_DENOISE_ARG_OFFSET)->guide_addr;
+}
+__device__ __forceinline__ uint32_t base_colours(const Scene& S) {
+  return (uint32_t)arg_at<rt_denoise_arg_t>(S, RT_DENOISE_ARG_OFFSET)->base_addr;
+}
+// The guide normal of triangle `pid` (rt_tri_t by pid in ptris), three signed bytes packed
+// x | y << 8 | z << 16: rt_path.h tri_normal's first three statements -- cross3, len =
+// sqrtf(dot3(n, n)), n / len, no facing flip -- then rintf(n_i * 127); 0 when len is 0 or
+// not finite.
+__device__ __forceinline__ uint32_t guide_normal(const Scene& S, int32_t pid) {
+  const uint32_t o = S.ptris + 48u * (uint32_t)pid;
+  const float4 b = S.A.ld_f4(o + 16), c = S.A.ld_f4(o + 32);
+  const float e1[3] = {b.x, b.y, b.z}, e2[3] = {c.x, c.y, c.z};
+  float n[3];
+  cross3(n, e1, e2);
+  const float len = sqrtf(dot3(n, n));
+  if (!(len > 0.0f && len < INFINITY)) return 0u;
+  uint32_t v = 0;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) v |= ((uint32_t)(int32_t)rintf((n[k] / len) * 127.0f) & 0xffu) << (8 * k);
+  return v;
+}
+#elif RT_AOV_BASE
 // the base-colour buffer, the same way
 __device__ __forceinline__ uint32_t base_colours(const Scene& S) {
   return (uint32_t)arg_at<rt_relight_arg_t>(S, RT_RELIGHT_ARG_OFFSET)->base_addr;
 }
 #endif
 
+#if RT_AOV_BASE != 2
 // one light's verdict for the wave's shadow rays: true where the light does not see the lane's point
 __device__ __forceinline__ bool light_occluded(const Scene& S, const Ray& p, float th, const float L[3],
                                                bool shadow, int32_t hit, uint32_t slist_on, uint32_t sidx,
@@ -71,6 +111,7 @@ __device__ __forceinline__ bool light_occluded(const Scene& S, const Ray& p, flo
                                       : occluded_packet(walk_scene(S), s, shadow, hit, 1.0f, cnt);
   return shadow && occ;
 }
+#endif
 
 __device__ __forceinline__ void kernel_body(const vx_task_t& task, const Scene& S, uint32_t nl, uint32_t aov,
                                             uint32_t base, Counters& cnt) {
@@ -95,6 +136,13 @@ __device__ __forceinline__ void kernel_body(const vx_task_t& task, const Scene& 
   const uint32_t color = shade_wave(S, spid, x, y, S.clear_color, cnt);
   if (in) S.A.st_u32(base + 4u * out, color);
 #endif
+#if RT_AOV_BASE == 2
+  // the guide record: a geometry pixel's normal is its winner's (lanes without one read nothing)
+  (void)nl;
+  const uint32_t gn = hit >= 0 ? guide_normal(S, hit) : 0u;
+  if (in) S.A.st_u4(aov + 16u * out, make_uint4((uint32_t)spid, hz | (hit >= 0 ? RT_AOV_GEOM : 0u), gn, 0u));
+  return;
+#else
 
   float th = 0.0f;
   uint32_t df = hz | (hit >= 0 ? RT_AOV_GEOM : 0u), mask = 0;
@@ -125,6 +173,7 @@ __device__ __forceinline__ void kernel_body(const vx_task_t& task, const Scene& 
     }
   }
   if (in) S.A.st_u4(aov + 16u * out, make_uint4((uint32_t)spid, df, __float_as_uint(th), mask));
+#endif
 }
 
 }  // namespace
@@ -134,7 +183,11 @@ VX_MAIN(rt_kernel_arg_t, arg, RT_BLOCK_THREADS) {
   Scene S = load_scene(arg, vx_launch_words);
   // (the tag is a kernel argument: the light count and the buffer stay in scalar registers)
   const uint32_t nl = vx_launch_tag < RT_MAX_LIGHTS ? vx_launch_tag : RT_MAX_LIGHTS;
+#if RT_AOV_BASE == 2
+  const uint32_t aov = guide_records(S);
+#else
   const uint32_t aov = aov_base(S);
+#endif
 #if RT_AOV_BASE
   const uint32_t base = base_colours(S);
 #else

@@ -389,6 +389,78 @@ static inline uint32_t rt_relight_occluded(uint32_t mask, const uint32_t w[4], u
     O += (i < n && ((mask >> i) & 1u)) ? (w[i >> 2] >> (8u * (i & 3u))) & 0xffu : 0u;
   return O;
 }
+// Denoising accumulated path frames (vx_rt.h rt_denoise_capture_start / rt_render_denoise_start).
+// The capture launch (rt_aov_kernel.hip RT_AOV_BASE=2, image rt_aov_guide) writes one 16-B guide
+// record per framebuffer pixel -- {pid, depth word | RT_AOV_GEOM, normal, 0}, the normal's three
+// signed bytes packed x | y << 8 | z << 16 -- and the pixel's base colour; the prepare and pass
+// launches (rt_denoise_kernel.hip, images rt_denoise_prep / rt_denoise_pass) work on the tap
+// records below.  Their argument area, behind the six above, which stay where they are: written
+// when the buffers are allocated, in stream order, constant until the next configure.  Every
+// buffer holds one entry per framebuffer pixel in framebuffer order (linear W * H only).
+typedef struct {
+  uint64_t guide_addr;   // 16 B: the guide record (rt_denoise_guide_t)
+  uint64_t base_addr;    // 4 B: the base colour (ARGB, the pixel shaded without shadows)
+  uint64_t tapg_addr;    // 8 B: what a tap needs of the guide: {pid, or RT_DN_NO_GEOM for a pixel
+                         // without RT_AOV_GEOM; depth word | normal x << 24}
+  uint64_t irr_addr[2];  // 8 B each, ping-pong: {I_R | I_G << 16, I_B | normal y << 16 | normal z << 24}
+                         // of a geometry pixel; {the resolved ARGB pixel, 0} of any other
+  uint32_t width, height;
+  uint32_t cbuf1_off;    // the second framebuffer past arg.cbuf_addr, mod 2^32 (RT_DN_TAG_CBUF1)
+  uint32_t pad;
+} rt_denoise_arg_t;
+#define RT_DENOISE_ARG_OFFSET (RT_RELIGHT_ARG_OFFSET + sizeof(rt_relight_arg_t))
+#define RT_DN_NO_GEOM 0xffffffffu
+// A pass launch's words: w[0] = zs (depth shift, 0..23), w[1] = ls (irradiance shift, 0..16);
+// its tag:
+#define RT_DN_TAG_K_MASK 0x7u   // bits 0-2: the pass k, 1..5 (stride 2^(k-1); input irr[(k-1)&1])
+#define RT_DN_TAG_LAST   0x8u   // bit 3: the last pass: remodulate and store to the framebuffer
+#define RT_DN_TAG_CBUF1  0x10u  // bit 4: the framebuffer in use is the second one
+#define RT_DN_MAX_PASSES 5u
+#define RT_DN_MAX_ZS 23u
+#define RT_DN_MAX_LS 16u
+// The filter's integer pieces (vx_rt.h states the definition; tests/denoise_reference.py restates
+// it in numpy from that text).  The kernels and the host share this text.
+// an edge stop: E(e) = e >= 9 ? 0 : 256 >> e
+#if defined(__HIPCC__)
+__host__ __device__
+#endif
+static inline uint32_t rt_dn_stop(uint32_t e) { return e >= 9u ? 0u : 256u >> e; }
+// byte k of a packed normal, sign-extended
+#if defined(__HIPCC__)
+__host__ __device__
+#endif
+static inline int32_t rt_dn_sbyte(uint32_t v, uint32_t k) { return (int32_t)(v << (24u - 8u * k)) >> 24; }
+// the normal stop between two packed normals (x | y << 8 | z << 16): c = min(256, |Np . Nq| >> 6),
+// wn = (c * c) >> 8, then wn = (wn * wn) >> 8
+#if defined(__HIPCC__)
+__host__ __device__
+#endif
+static inline uint32_t rt_dn_wn(uint32_t np, uint32_t nq) {
+  const int32_t d = rt_dn_sbyte(np, 0) * rt_dn_sbyte(nq, 0) + rt_dn_sbyte(np, 1) * rt_dn_sbyte(nq, 1) +
+                    rt_dn_sbyte(np, 2) * rt_dn_sbyte(nq, 2);
+  uint32_t c = (uint32_t)(d < 0 ? -d : d) >> 6;
+  c = c > 256u ? 256u : c;
+  const uint32_t w = (c * c) >> 8;
+  return (w * w) >> 8;
+}
+// one channel's irradiance: the mean s / n over the albedo a / 256, I = min(65535, (256 * s +
+// d / 2) / d) with d = n * max(a, 1); 256 * s reaches 2^40 (s <= 255 * 2^24), so 64 bits
+#if defined(__HIPCC__)
+__host__ __device__
+#endif
+static inline uint32_t rt_dn_demod(uint32_t s, uint32_t n, uint32_t a) {
+  const uint64_t d = (uint64_t)(n ? n : 1u) * (a ? a : 1u);
+  const uint64_t q = (256u * (uint64_t)s + d / 2u) / d;
+  return q > 65535u ? 65535u : (uint32_t)q;
+}
+// one channel remodulated: min(255, (I * a + 128) >> 8)
+#if defined(__HIPCC__)
+__host__ __device__
+#endif
+static inline uint32_t rt_dn_remod(uint32_t I, uint32_t a) {
+  const uint32_t v = (I * a + 128u) >> 8;
+  return v > 255u ? 255u : v;
+}
 // A path-traced frame lit by several point lights (pt_kernel.hip PT_LIGHTS, images pt_lights /
 // pt_lights_accum; vx_rt.h rt_renderer_set_path_lights) reads the first count <=
 // RT_MAX_PATH_LIGHTS entries of the same table, every one with lists (slist_on 1).  The cap is

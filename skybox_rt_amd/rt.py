@@ -85,6 +85,9 @@ RT_MAX_LIGHTS = 16
 RT_MAX_PATH_LIGHTS = 8
 # rt_aov_t (vx_rt.h): one visibility record per framebuffer pixel
 AOV_DTYPE = np.dtype([("pid", "<i4"), ("depth_flags", "<u4"), ("t", "<f4"), ("light_mask", "<u4")])
+# a denoise guide record (vx_rt.h rt_denoise_guide_t): normal = signed bytes x | y << 8 | z << 16
+DENOISE_GUIDE_DTYPE = np.dtype([("pid", "<i4"), ("depth_flags", "<u4"), ("normal", "<u4"), ("reserved", "<u4")])
+DENOISE_PASSES, DENOISE_DEPTH_SHIFT, DENOISE_COLOR_SHIFT = 2, 2, 3   # vx_rt.h RT_DENOISE_DEFAULT_*
 RT_AOV_DEPTH_MASK = 0xFFFFFF
 RT_AOV_GEOM = 0x01000000
 RT_AOV_SHADOW_RAY = 0x02000000
@@ -184,6 +187,12 @@ def lib():
             "rt_render_relight_start": [vp, vp, u32],
             "rt_render_relight": [vp, vp, u32],
             "rt_read_relight_base": [vp, vp, u64],
+            "rt_denoise_capture_start": [vp],
+            "rt_denoise_capture": [vp],
+            "rt_render_denoise_start": [vp, vp],
+            "rt_render_denoise": [vp, vp],
+            "rt_read_denoise_guide": [vp, vp, vp, u64],
+            "rt_write_accum": [vp, vp, u64, u32],
         }
         for name, argtypes in sig.items():
             fn = getattr(h, name)
@@ -658,6 +667,57 @@ class Renderer:
         out = np.zeros((p.height, p.width), np.uint32)
         _check(lib().rt_read_relight_base(self._h, out.ctypes.data, out.size), "rt_read_relight_base")
         return out
+
+    # denoising accumulated path frames (vx_rt.h rt_denoise_capture_start; images rt_aov_guide,
+    # rt_denoise_prep, rt_denoise_pass)
+    def denoise_capture(self, wait: bool = True) -> None:
+        """One launch writing the filter's guide -- per pixel the shaded
+        primitive, the depth word and geometry flag, the geometric normal -- and
+        the base colour (the pixel shaded without shadows) of the configured path
+        frame (linear framebuffer).  It depends on view and size only: lights,
+        resets and further samples leave it valid; configure() releases it."""
+        if wait:
+            _check(lib().rt_denoise_capture(self._h), "rt_denoise_capture")
+        else:
+            _check(lib().rt_denoise_capture_start(self._h), "rt_denoise_capture_start")
+
+    def denoise(self, passes: int = DENOISE_PASSES, depth_shift: int = DENOISE_DEPTH_SHIFT,
+                color_shift: int = DENOISE_COLOR_SHIFT, wait: bool = True) -> None:
+        """The edge-avoiding a-trous filter over the accumulated samples into
+        the framebuffer in use: 1 + passes launches, no tracing, no host wait, no
+        copy; the records are only read, accumulate() goes on afterwards.
+        passes 1..5 (strides 1, 2, 4, 8, 16), depth_shift 0..23, color_shift
+        0..16 (16: the irradiance stop is off).  wait=False: queued only."""
+        vals = (passes, depth_shift, color_shift)
+        if any(int(v) != v or v < 0 or v > 0xFFFFFFFF for v in vals):
+            raise RtError("rt_render_denoise failed: passes, depth_shift and color_shift are small integers")
+        prm = (C.c_uint32 * 3)(*[int(v) for v in vals])
+        fn = lib().rt_render_denoise if wait else lib().rt_render_denoise_start
+        _check(fn(self._h, C.addressof(prm)), "rt_render_denoise" if wait else "rt_render_denoise_start")
+
+    def denoise_guide(self):
+        """(guide, base) of the last denoise_capture() (waits for the device):
+        the guide records as a structured array (DENOISE_GUIDE_DTYPE) [H, W] and
+        the base colours uint32 ARGB [H, W]."""
+        p = self.params
+        if p is None:
+            raise RtError("rt_read_denoise_guide failed: renderer not configured")
+        guide = np.zeros((p.height, p.width), DENOISE_GUIDE_DTYPE)
+        base = np.zeros((p.height, p.width), np.uint32)
+        _check(lib().rt_read_denoise_guide(self._h, guide.ctypes.data, base.ctypes.data, base.size),
+               "rt_read_denoise_guide")
+        return guide, base
+
+    def write_accum(self, rec) -> None:
+        """Restore the accumulation records (checkpoint and resume): uint32
+        [H, W, 4] (or the flat compact array) as accum() returns them, every
+        record with the same n in 1..2^24, which becomes the sample cursor -- the
+        next accumulate() continues from it.  Waits for the device."""
+        a = np.ascontiguousarray(rec, np.uint32)
+        if a.ndim < 2 or a.shape[-1] != 4 or a.size == 0:
+            raise RtError("rt_write_accum failed: records are uint32 [..., 4]")
+        n = int(a.reshape(-1, 4)[0, 3])
+        _check(lib().rt_write_accum(self._h, a.ctypes.data, a.size // 4, n), "rt_write_accum")
 
     def stats(self) -> dict:
         s = Stats()
