@@ -135,6 +135,13 @@ int rt_scene_setup_prims(rt_scene_h scene, uint32_t width, uint32_t height, int3
  * NULL: row-major), 16 chunks a tile; count = records `out` holds, *size = records written */
 int rt_scene_bg_layers(rt_scene_h scene, uint32_t width, uint32_t height, const uint32_t* order,
                        uint32_t first_chunk, uint32_t* out, uint64_t count, uint64_t* size);
+/* the per-block candidate lists of a width x height frame and the same lists trimmed to their winners
+ * (RT_REC_BIDX, RT_REC_BLIST, RT_REC_BTIDX, RT_REC_BTRIM of one shard), on the host alone: *entries =
+ * the untrimmed lists' entries (blist and btrim hold entries + 3 padding records of uint32[4]), *blocks
+ * = the shard's 8x8 blocks (bidx and btidx hold uint32[2] each).  NULL arrays: sizes only.  NO REFERENCE. */
+int rt_scene_block_trim(rt_scene_h scene, uint32_t width, uint32_t height, uint32_t shard_index,
+                        uint32_t shard_count, uint32_t* bidx, uint32_t* blist, uint32_t* btidx, uint32_t* btrim,
+                        uint64_t* entries, uint64_t* blocks);
 /* primary-visibility record of every primitive at width x height (the RT
  * kernels' raster-exact primary rays, rt_common.h): uint32[num_prims][3] =
  * covered-pixel rectangle x0 | x1 << 16, y0 | y1 << 16 (inclusive; empty:
@@ -358,6 +365,10 @@ typedef struct {
   uint32_t tier_groups;   /* the geometry tier's workgroups (the launch tag) of a frame started
                              on a launch lane -- with env RT_BG_TIER=2 of a frame rendered alone
                              -- now; 0: that frame is untiered */
+  uint64_t btrim_entries; /* the trimmed block lists (RT_REC_BTRIM) the frames scan: the entries kept --
+                             0: no trim (no lists, RT_RENDER_INSTRUMENTED, env RT_BLIST_TRIM=0) */
+  uint32_t btrim_blocks;  /* ... and the blocks that keep any */
+  uint32_t pad;
 } rt_setup_stats_t;
 /* (reads back the status of shadow lists queued by rt_renderer_set_light:
  * waits for the device) */
@@ -722,6 +733,12 @@ int rt_write_accum(rt_renderer_h r, const uint32_t* rec, uint64_t count, uint32_
 #define RT_REC_BGLAYER 18u  /* background tier: uint32[2] per chunk from the first background chunk on, in work
                              * order, as the device setup built it: pid + 1 of the one screen layer covering the
                              * chunk's 8x8 block (0xffffffff: none, 0: mixed or off the image), its drawcall */
+#define RT_REC_BTIDX 20u    /* the trimmed block lists' headers: uint32[2] per local 8x8 block -- RT_REC_BIDX's
+                             * first entry, the kept count */
+#define RT_REC_BTRIM 21u    /* the trimmed block lists (RT_REC_BLIST's shape): per block the entries whose
+                             * primitive wins a pixel of the block, moved to the front of the list's slots */
+#define RT_REC_BTIDX_HOST 22u /* the same two arrays restated on the host from the device's untrimmed lists */
+#define RT_REC_BTRIM_HOST 23u
 #define RT_REC_BGLAYER_HOST 19u /* the same table restated on the host from the work order and the layer records */
 int rt_renderer_export_records(rt_renderer_h r, uint32_t which, void* out, uint64_t bytes,
                                uint64_t* size);

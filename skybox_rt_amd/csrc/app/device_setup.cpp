@@ -545,6 +545,50 @@ int chunk_desc(rt_renderer* r, uint32_t* launches) {
   return 0;
 }
 
+int block_trim(rt_renderer* r, uint32_t* launches) {
+  rt_kernel_arg_t& a = r->arg;
+  if (!a.blist_blocks || !r->btrim_img) return 0;
+  const uint64_t entries = r->setup.blist_entries;
+  // the launch's own argument buffer: the render arguments under the whole-block task map over
+  // every local block, in block order, with the untrimmed lists; the trim's area behind them
+  struct {
+    rt_kernel_arg_t a;
+    rt_btrim_arg_t t;
+  } b;
+  static_assert(offsetof(decltype(b), t) == RT_BTRIM_ARG_OFFSET, "the trim's area stands right behind the block");
+  uint64_t args = 0, btrim = 0, btidx = 0;
+  if (ensure(r, sizeof(b), &r->btrim_args, &args) || ensure(r, (entries + RT_BLIST_PAD) * sizeof(rt_bentry_t), &r->btrim, &btrim) ||
+      ensure(r, (uint64_t)a.blist_blocks * 8, &r->btidx, &btidx))
+    return -1;
+  std::memset(&b, 0, sizeof(b));
+  b.a = a;
+  b.a.order_addr = 0;
+  b.a.split_tiles = b.a.quad_tiles = 0;
+  b.a.cdesc_addr = 0;
+  b.a.cdesc_first = 0;
+  b.a.num_tasks = a.blist_blocks * 64u;
+  b.t.btrim_addr = btrim;
+  b.t.btidx_addr = btidx;
+  b.t.stat_addr = args + RT_BTRIM_ARG_OFFSET + offsetof(rt_btrim_arg_t, stat);
+  b.t.entries = (uint32_t)entries;
+  if (write_buf(r, r->btrim_args, 0, &b, sizeof(b)) != 0) return set_error("trim argument upload failed");
+  // an ordinary launch on the image's grid, untimed, behind the setup sequence in stream order
+  const uint32_t lw[4] = {0, 0, 0, 0};
+  if (r->set_counters && r->set_counters(r->dev, 0) != 0) return set_error("vx_hip_set_counters failed");
+  if (r->set_words && r->set_words(r->dev, lw, 4) != 0) return set_error("vx_hip_set_launch_words failed");
+  if (r->set_tag && r->set_tag(r->dev, 0) != 0) return set_error("vx_hip_set_launch_tag failed");
+  const bool grouped = r->launch_group && r->launch_group(r->dev, 1u | VX_HIP_GROUP_UNTIMED) == 0;
+  if (vx_start(r->dev, r->btrim_img, r->btrim_args) != 0) {
+    if (grouped) r->launch_group(r->dev, 0);
+    return set_error("vx_start failed");
+  }
+  ++*launches;
+  a.blist_addr = btrim;
+  a.bidx_addr = btidx;
+  r->trim_on = true;
+  return 0;
+}
+
 int bg_layers(rt_renderer* r, uint32_t first, uint64_t* addr, uint32_t* launches) {
   const rt_kernel_arg_t& a = r->arg;
   *addr = 0;

@@ -410,6 +410,15 @@ int rt_renderer_create(rt_scene_h s, const char* kernel_dir, rt_renderer_h* out)
   const char* sv = std::getenv("RT_SETUP");
   const bool host_records = sv && std::string(sv) == "host";
   if (rtapp::device_ingest(r.get(), !host_records) != 0) return -1;
+  // the block-list trim's image (rt_btrim_kernel.hip), by the per-file rule; its module is loaded here
+  // (asking for its launch shape does), so that the first configure does not pay for it
+  if (upload_image(r.get(), rtimg::resolve_file(r->kdir, lib_dir(), "rt_btrim.vxbin", file_exists), &r->btrim_img) != 0)
+    return -1;
+  {
+    uint64_t ia = 0;
+    uint32_t block = 0, grid = 0;
+    if (r->launch_shape && vx_mem_address(r->btrim_img, &ia) == 0) r->launch_shape(r->dev, ia, &block, &grid);
+  }
   if (host_records) {
     std::vector<rt_tri_t> pt(s->scene.prims.size());
     for (size_t g = 0; g < pt.size(); ++g) {
@@ -535,6 +544,15 @@ int rt_renderer_setup_stats(rt_renderer_h r, rt_setup_stats_t* st) {
   if (!r || !st) return fail("null argument");
   if (!r->configured) return fail("renderer not configured");
   if (rtapp::settle_lists(r) != 0) return -1;
+  if (r->trim_on && !r->trim_counted) {
+    // the trim launch's two counters, behind its argument block (waits for the device)
+    uint32_t c[2] = {0, 0};
+    if (vx_copy_from_dev(c, r->btrim_args, RT_BTRIM_ARG_OFFSET + offsetof(rt_btrim_arg_t, stat), sizeof(c)) != 0)
+      return fail("vx_copy_from_dev failed");
+    r->setup.btrim_entries = c[0];
+    r->setup.btrim_blocks = c[1];
+    r->trim_counted = true;
+  }
   r->setup.slist_on = r->arg.slist_on;
   r->setup.slist_stale = r->sl_stale ? 1u : 0u;
   r->setup.lane_grid = lane_grid_of(r);
@@ -746,6 +764,13 @@ int rt_renderer_export_records(rt_renderer_h r, uint32_t which, void* out, uint6
       b = a.blist_blocks ? r->blist : nullptr;
       n = (r->setup.blist_entries + RT_BLIST_PAD) * sizeof(rt_bentry_t);
       break;
+    case RT_REC_BTIDX:
+    case RT_REC_BTIDX_HOST: b = r->trim_on ? r->btidx : nullptr; n = (uint64_t)a.blist_blocks * 8; break;
+    case RT_REC_BTRIM:
+    case RT_REC_BTRIM_HOST:
+      b = r->trim_on ? r->btrim : nullptr;
+      n = (r->setup.blist_entries + RT_BLIST_PAD) * sizeof(rt_bentry_t);
+      break;
     case RT_REC_SIDX: b = a.slist_on ? r->sidx : nullptr; n = 6ull * a.slist_n * a.slist_n * 8; break;
     case RT_REC_SLIST: b = a.slist_on ? r->slist : nullptr; n = (r->sl_entries + 1) * sizeof(rt_tri_t); break;
     case RT_REC_CDESC:
@@ -763,15 +788,36 @@ int rt_renderer_export_records(rt_renderer_h r, uint32_t which, void* out, uint6
   if (which == RT_REC_CDESC_HOST && out) {
     // the host restatement (app/setup.cpp ChunkDescs) from the device's work order and list headers
     if (bytes < n) return fail("buffer too small");
+    // (the headers the frames read: the trimmed lists' while those are in use)
     std::vector<uint32_t> order(a.order_addr ? r->local_tiles : 0u), bidx((size_t)a.blist_blocks * 2);
     if ((!order.empty() && vx_copy_from_dev(order.data(), r->order, 0, order.size() * 4) != 0) ||
-        (!bidx.empty() && vx_copy_from_dev(bidx.data(), r->bidx, 0, bidx.size() * 4) != 0))
+        (!bidx.empty() && vx_copy_from_dev(bidx.data(), r->trim_on ? r->btidx : r->bidx, 0, bidx.size() * 4) != 0))
       return fail("vx_copy_from_dev failed");
     const std::vector<rt_cdesc_t> d = rt::ChunkDescs(
         a.width, a.tiles_x, a.shard_index, a.shard_count, (a.flags & RT_FLAG_COMPACT) != 0, a.split_tiles,
         r->local_tiles, order.empty() ? nullptr : order.data(), bidx.empty() ? nullptr : bidx.data());
     if (d.size() * sizeof(rt_cdesc_t) != n) return fail("chunk descriptor count mismatch");
     std::memcpy(out, d.data(), n);
+    if (size) *size = n;
+    return 0;
+  }
+  if ((which == RT_REC_BTRIM_HOST || which == RT_REC_BTIDX_HOST) && out) {
+    // the host restatement (app/setup.cpp TrimBlockLists) from the device's untrimmed lists and vgeom records
+    if (bytes < n) return fail("buffer too small");
+    const uint64_t entries = r->setup.blist_entries;
+    std::vector<uint32_t> bidx((size_t)a.blist_blocks * 2), ti;
+    std::vector<rt_bentry_t> ent(entries + RT_BLIST_PAD), te;
+    std::vector<rt_vtri_t> vg(r->sc->geometry.size());
+    if (vx_copy_from_dev(bidx.data(), r->bidx, 0, bidx.size() * 4) != 0 ||
+        vx_copy_from_dev(ent.data(), r->blist, 0, ent.size() * sizeof(rt_bentry_t)) != 0 ||
+        vx_copy_from_dev(vg.data(), r->vgeom, 0, vg.size() * sizeof(rt_vtri_t)) != 0)
+      return fail("vx_copy_from_dev failed");
+    uint64_t kept = 0;
+    uint32_t blocks = 0;
+    rt::TrimBlockLists(a.width, a.height, a.tiles_x, a.shard_index, a.shard_count, r->local_tiles, r->sc->tie_high,
+                       bidx.data(), ent.data(), entries, vg.data(), &ti, &te, &kept, &blocks);
+    if (which == RT_REC_BTRIM_HOST) std::memcpy(out, te.data(), n);
+    else std::memcpy(out, ti.data(), n);
     if (size) *size = n;
     return 0;
   }
@@ -849,6 +895,51 @@ int rt_scene_bg_layers(rt_scene_h s, uint32_t width, uint32_t height, const uint
   if (count < d.size()) return fail("buffer too small");
   std::memcpy(out, d.data(), d.size() * sizeof(rt_bglayer_t));
   if (size) *size = d.size();
+  return 0;
+}
+
+static void host_block_lists(const rt_scene* s, const std::vector<rt::VisPrim>& vis, uint32_t tiles_x,
+                             uint32_t local_tiles, uint32_t si, uint32_t sc, std::vector<uint32_t>* idxo,
+                             std::vector<rt_bentry_t>* ento, uint64_t* totalo, uint64_t* longesto);
+
+int rt_scene_block_trim(rt_scene_h s, uint32_t width, uint32_t height, uint32_t shard_index, uint32_t shard_count,
+                        uint32_t* bidx, uint32_t* blist, uint32_t* btidx, uint32_t* btrim, uint64_t* entries,
+                        uint64_t* blocks) {
+  if (!s || width == 0 || height == 0 || shard_count == 0 || shard_index >= shard_count) return fail("bad argument");
+  const uint32_t tiles_x = (width + 31u) / 32u, tiles = tiles_x * ((height + 31u) / 32u);
+  const uint32_t local_tiles = tiles > shard_index ? (tiles - shard_index + shard_count - 1) / shard_count : 0;
+  std::vector<rt_prim_t> prims(s->scene.prims.size());
+  std::vector<rt::VisPrim> vis(prims.size());
+  for (size_t d = 0; d < s->scene.drawcalls.size(); ++d) {
+    const rt::DrawCall& dc = s->scene.drawcalls[d];
+    for (uint32_t i = 0; i < dc.prim_count; ++i) {
+      const uint32_t g = dc.prim_offset + i;
+      rt_bbox_t bb{0, 0};
+      const bool ok = rt::PrimSetup(s->scene.prims[g], width, height, dc.viewport[4], dc.viewport[5],
+                                    &prims[g]) == rt::kSetupOk &&
+                      rt::PrimBBox(s->scene.prims[g], width, height, &bb) == rt::kSetupOk;
+      prims[g].dc = (uint32_t)d;
+      vis[g] = rt::ComputeVisPrim(prims[g], ok, bb, width, height);
+    }
+  }
+  std::vector<rt_bentry_t> ent, te;
+  std::vector<uint32_t> idx, ti;
+  uint64_t total = 0, longest = 0;
+  host_block_lists(s, vis, tiles_x, local_tiles, shard_index, shard_count, &idx, &ent, &total, &longest);
+  if (ent.empty()) return fail("rt_scene_block_trim: the block lists do not fit (RT_BLIST_MAX_LIST, RT_BLIST_MAX_ENTRIES)", -2);
+  if (entries) *entries = total;
+  if (blocks) *blocks = (uint64_t)local_tiles * 16u;
+  if (!bidx && !blist && !btidx && !btrim) return 0;
+  std::vector<rt_vtri_t> vg;
+  for (int32_t g : s->geometry) vg.push_back(rt::MakeVisTri(prims[g], vis[g], g));
+  uint64_t kept = 0;
+  uint32_t kb = 0;
+  rt::TrimBlockLists(width, height, tiles_x, shard_index, shard_count, local_tiles, s->tie_high, idx.data(),
+                     ent.data(), total, vg.data(), &ti, &te, &kept, &kb);
+  if (bidx) std::memcpy(bidx, idx.data(), idx.size() * 4);
+  if (blist) std::memcpy(blist, ent.data(), ent.size() * sizeof(rt_bentry_t));
+  if (btidx) std::memcpy(btidx, ti.data(), ti.size() * 4);
+  if (btrim) std::memcpy(btrim, te.data(), te.size() * sizeof(rt_bentry_t));
   return 0;
 }
 
@@ -1081,17 +1172,23 @@ static int configure_vis(rt_renderer* r, const std::vector<rt_prim_t>& prims,
 // vis_build_lists): for every local block of the shard, the geometry
 // primitives whose covered rectangle reaches it, ascending (depth bound,
 // geometry index), each with the union rectangle of itself and the rest.
-static int build_block_lists(rt_renderer* r, const std::vector<rt::VisPrim>& vis) {
-  const rt_scene* s = r->sc;
-  rt_kernel_arg_t& a = r->arg;
-  const uint32_t nblk = r->local_tiles * 16u, sc = a.shard_count, si = a.shard_index;
+// (the lists alone, from the scene and its visibility records: *ent with the padding entries, unless
+// the lists do not fit -- block_lists_fit -- and stay empty)
+static void host_block_lists(const rt_scene* s, const std::vector<rt::VisPrim>& vis, uint32_t tiles_x,
+                             uint32_t local_tiles, uint32_t si, uint32_t sc, std::vector<uint32_t>* idxo,
+                             std::vector<rt_bentry_t>* ento, uint64_t* totalo, uint64_t* longesto) {
+  std::vector<rt_bentry_t>& ent = *ento;
+  std::vector<uint32_t>& idx = *idxo;
+  ent.clear();
+  idx.clear();
+  const uint32_t nblk = local_tiles * 16u;
   std::vector<std::vector<std::pair<uint32_t, uint32_t>>> lists(nblk);  // (zmin, k)
   for (uint32_t k = 0; k < (uint32_t)s->geometry.size(); ++k) {
     const rt::VisPrim& v = vis[s->geometry[k]];
     if (!v.any) continue;
     for (uint32_t by = (v.ry & 0xffffu) >> 3; by <= (v.ry >> 16) >> 3; ++by)
       for (uint32_t bx = (v.rx & 0xffffu) >> 3; bx <= (v.rx >> 16) >> 3; ++bx) {
-        const uint32_t t = (by >> 2) * a.tiles_x + (bx >> 2);
+        const uint32_t t = (by >> 2) * tiles_x + (bx >> 2);
         if (t % sc != si) continue;
         lists[((t / sc) << 4) | ((by & 3u) << 2) | (bx & 3u)].push_back({v.zmin, k});
       }
@@ -1101,12 +1198,9 @@ static int build_block_lists(rt_renderer* r, const std::vector<rt::VisPrim>& vis
     total += l.size();
     longest = std::max<uint64_t>(longest, l.size());
   }
-  r->setup.blist_max = (uint32_t)longest;
-  r->setup.blist_entries = total;
-  a.blist_blocks = 0;
-  if (!rtapp::block_lists_fit(longest, total)) return 0;
-  std::vector<rt_bentry_t> ent;
-  std::vector<uint32_t> idx;
+  *totalo = total;
+  *longesto = longest;
+  if (!rtapp::block_lists_fit(longest, total)) return;
   ent.reserve(total + RT_BLIST_PAD);
   idx.reserve(2 * (size_t)nblk);
   for (auto& l : lists) {
@@ -1125,10 +1219,42 @@ static int build_block_lists(rt_renderer* r, const std::vector<rt::VisPrim>& vis
   }
   for (uint32_t i = 0; i < RT_BLIST_PAD; ++i)
     ent.push_back(rt_bentry_t{0u, RT_BLIST_PAD_LO, RT_BLIST_PAD_HI, RT_VIS_ZMIN_NONE});
+}
+
+// trim: the lists trimmed to their winners beside them (app/setup.cpp TrimBlockLists over the vgeom
+// records `prims` and `vis` give), and the render arguments pointed at those
+static int build_block_lists(rt_renderer* r, const std::vector<rt_prim_t>& prims, const std::vector<rt::VisPrim>& vis,
+                             bool trim) {
+  const rt_scene* s = r->sc;
+  rt_kernel_arg_t& a = r->arg;
+  std::vector<rt_bentry_t> ent;
+  std::vector<uint32_t> idx;
+  uint64_t total = 0, longest = 0;
+  host_block_lists(s, vis, a.tiles_x, r->local_tiles, a.shard_index, a.shard_count, &idx, &ent, &total, &longest);
+  r->setup.blist_max = (uint32_t)longest;
+  r->setup.blist_entries = total;
+  a.blist_blocks = 0;
+  if (ent.empty()) return 0;
   if (upload(r->dev, ent.data(), ent.size() * sizeof(rt_bentry_t), &r->blist, &a.blist_addr) ||
       upload(r->dev, idx.data(), idx.size() * 4, &r->bidx, &a.bidx_addr))
     return -1;
-  a.blist_blocks = nblk;
+  a.blist_blocks = r->local_tiles * 16u;
+  if (!trim) return 0;
+  std::vector<rt_vtri_t> vg;
+  for (int32_t g : s->geometry) vg.push_back(rt::MakeVisTri(prims[g], vis[g], g));
+  std::vector<rt_bentry_t> te;
+  std::vector<uint32_t> ti;
+  uint64_t kept = 0;
+  uint32_t blocks = 0;
+  rt::TrimBlockLists(a.width, a.height, a.tiles_x, a.shard_index, a.shard_count, r->local_tiles, s->tie_high,
+                     idx.data(), ent.data(), total, vg.data(), &ti, &te, &kept, &blocks);
+  if (upload(r->dev, te.data(), te.size() * sizeof(rt_bentry_t), &r->btrim, &a.blist_addr) ||
+      upload(r->dev, ti.data(), ti.size() * 4, &r->btidx, &a.bidx_addr))
+    return -1;
+  r->trim_on = true;
+  r->trim_counted = true;
+  r->setup.btrim_entries = kept;
+  r->setup.btrim_blocks = blocks;
   return 0;
 }
 
@@ -1160,7 +1286,7 @@ static int build_tail_lists(rt_renderer* r) {
 // (RT_RENDER_HOST_SETUP / env RT_SETUP=host, and the RT_VIS_TREE=screen
 // variant, which needs the visibility records on the host).
 static int host_setup(rt_renderer* r, const rt_render_params_t* p, bool raster, bool order_on, bool lists,
-                      uint32_t* heavy) {
+                      bool trim, uint32_t* heavy) {
   const rt_scene* s = r->sc;
   rt_kernel_arg_t& a = r->arg;
   // per-resolution shading records (rast_prim_t + drawcall id)
@@ -1230,7 +1356,7 @@ static int host_setup(rt_renderer* r, const rt_render_params_t* p, bool raster, 
     while (*heavy < r->local_tiles && w(ord[*heavy]) > 0) ++*heavy;
   }
   if (!raster && configure_vis(r, prims, vis, r->use_bvh4) != 0) return -1;
-  if (lists && build_block_lists(r, vis) != 0) return -1;
+  if (lists && build_block_lists(r, prims, vis, trim) != 0) return -1;
   // output buffer, pre-filled with the clear colour (draw3d/main.cpp:485-490)
   std::vector<uint32_t> clear(r->cbuf_bytes / 4 ? r->cbuf_bytes / 4 : 1, p->clear_color);
   if (upload(r->dev, clear.data(), r->cbuf_bytes, &r->cbuf, &a.cbuf_addr)) return -1;
@@ -1376,6 +1502,14 @@ int rt_renderer_configure(rt_renderer_h r, const rt_render_params_t* p) {
   r->cdesc_n = 0;
   r->setup.blist_entries = 0;
   r->setup.blist_max = 0;
+  // the lists trimmed to their winners for every configuration that renders
+  // from them, unless instrumented -- those frames scan the untrimmed lists, so their counters
+  // stay the oracle's -- or env RT_BLIST_TRIM=0 (the A/B switch)
+  const char* bte = std::getenv("RT_BLIST_TRIM");
+  const bool trim = lists && !(p->flags & RT_RENDER_INSTRUMENTED) && !(bte && std::atoi(bte) == 0);
+  r->trim_on = r->trim_counted = false;
+  r->setup.btrim_entries = 0;
+  r->setup.btrim_blocks = 0;
   // shadow rays (primary+shadow frames, every path vertex): light-space
   // lists (built on the device for this light; env RT_SHADOW_LISTS=0 keeps
   // the BVH walks; the host setup path walks the BVH)
@@ -1392,7 +1526,9 @@ int rt_renderer_configure(rt_renderer_h r, const rt_render_params_t* p) {
     r->vis_refs.clear();
     r->vis_pids.clear();
     if (rtapp::device_setup(r, raster, order_on, lists, slists, &heavy, &launches) != 0) return -1;
-  } else if (host_setup(r, p, raster, order_on, lists, &heavy) != 0) {
+    // (behind BSORT and any overflow refill, ahead of the chunk table's launch, which reads the headers)
+    if (trim && rtapp::block_trim(r, &launches) != 0) return -1;
+  } else if (host_setup(r, p, raster, order_on, lists, trim, &heavy) != 0) {
     return -1;
   }
   a.oidx_addr = a.olist_addr = a.ovtris_addr = 0;

@@ -144,6 +144,14 @@ struct rt_renderer {
   vx_buffer_h order = nullptr;
   vx_buffer_h vnodes = nullptr, vtris = nullptr, vlayers = nullptr, vgeom = nullptr;
   vx_buffer_h blist = nullptr, bidx = nullptr;  // per-block candidate lists (rt_bentry_t)
+  // the block lists trimmed to their winners (setup_common.h rt_btrim_arg_t; device_setup.cpp block_trim,
+  // rt_app.cpp host_block_trim): btrim / btidx beside blist / bidx, which stay the untrimmed lists;
+  // while trim_on the render arguments' list and header addresses are btrim's and btidx's.  The
+  // rt_btrim image is loaded at creation and kept (not an image a frame runs, so not in img[]);
+  // btrim_args: its argument buffer, whose last words count the kept entries and blocks
+  vx_buffer_h btrim = nullptr, btidx = nullptr, btrim_img = nullptr, btrim_args = nullptr;
+  bool trim_on = false;
+  bool trim_counted = false;     // setup.btrim_entries / btrim_blocks hold this configuration's counts
   vx_buffer_h cdesc = nullptr;   // chunk descriptor table (rt_cdesc_t, device_setup.cpp chunk_desc)
   uint32_t cdesc_n = 0;          // its records (0: none in this configuration)
   vx_buffer_h bglayer = nullptr; // background-layer table (rt_bglayer_t, device_setup.cpp bg_layers)
@@ -250,7 +258,7 @@ struct rt_renderer {
     vx_buffer_h* bufs[] = {&nodes, &nodes4, &tris, &layers, &dcs, &tex, &ptris, &geom, &oms, &bbox, &zbuf,
                            &order, &vnodes, &vtris, &vlayers, &vgeom, &gather_recv, &gather_image, &prims,
                            &cbuf, &cbuf1, &args, &verts, &pdc, &dcz, &layer_list, &geometry_list, &vis,
-                           &blist, &bidx, &cdesc, &bglayer, &sidx, &slist, &pathq, &pathq_ctr, &oidx, &olist, &ovtris,
+                           &blist, &bidx, &btrim, &btidx, &btrim_img, &btrim_args, &cdesc, &bglayer, &sidx, &slist, &pathq, &pathq_ctr, &oidx, &olist, &ovtris,
                            &accum, &aov, &aov_img, &relight_base, &aov_base_img, &relight_img,
                            &dn_guide_img, &dn_prep_img, &dn_pass_img, &dn_buf};
     for (auto* b : bufs) {
@@ -316,6 +324,11 @@ int device_ingest(rt_renderer* r, bool records);
 // rt_cdesc_t), one more launch of the setup image behind the configure's
 // sequence; called once the tiers are known, when the block lists are in use
 int chunk_desc(rt_renderer* r, uint32_t* launches);
+// the block lists trimmed to their winners (kernels/rt_btrim_kernel.hip), one launch behind the
+// configure's sequence and ahead of chunk_desc's: btrim / btidx built from blist / bidx, and the
+// render arguments' list and header addresses pointed at them (r->trim_on).  Called when the
+// lists are in use and final (after an overflow refill).
+int block_trim(rt_renderer* r, uint32_t* launches);
 // the background-layer table (rt_common.h rt_bglayer_t) of the chunks from `first` on, one more
 // launch behind chunk_desc's once the heavy tiles are known; *addr 0 and no records when the
 // configuration has no chunk table over every chunk

@@ -300,4 +300,76 @@ std::vector<rt_bglayer_t> BgLayers(uint32_t width, uint32_t height, uint32_t til
   return out;
 }
 
+namespace {
+// gfx_device.h fx_from_float_dev / fx_to_float / interp and rt_trace.h vis_depth on the host: the
+// shader's depth word from the three edge values (fp32, no contraction, IEEE division)
+int32_t FxFromFloatDev(float f, int frac) {
+  const float x = f * (float)(1u << frac);
+  if (x != x || x >= 2147483648.0f) return INT32_MAX;  // fcvt.w.s: NaN and overflow saturate high
+  if (x <= -2147483648.0f) return INT32_MIN;
+  return (int32_t)x;
+}
+int32_t Imadd24(int32_t a, int32_t b, int32_t c) {
+  const int32_t p = (int32_t)(((int64_t)a * (int64_t)b) >> 24);
+  return (int32_t)((uint32_t)p + (uint32_t)c);
+}
+uint32_t VisDepth(int32_t E0, int32_t E1, int32_t E2, const int32_t z[3]) {
+  const float k = 1.0f / (float)(1u << 24);
+  const float f0 = (float)E0 * k, f1 = (float)E1 * k, f2 = (float)E2 * k;
+  const float r = 1.0f / (f0 + f1 + f2);
+  const int32_t dx = FxFromFloatDev(r * f0, 24), dy = FxFromFloatDev(r * f1, 24);
+  return (uint32_t)Imadd24(z[1], dy, Imadd24(z[0], dx, z[2])) & VX_OM_DEPTH_MASK;
+}
+int32_t EdgeEval(const int32_t* e, uint32_t x, uint32_t y) {
+  return (int32_t)((uint32_t)e[0] * x + (uint32_t)e[1] * y + (uint32_t)e[2]);
+}
+bool RectIn(uint32_t r, uint32_t p) { return p >= (r & 0xffffu) && p <= (r >> 16); }
+}  // namespace
+
+void TrimBlockLists(uint32_t width, uint32_t height, uint32_t tiles_x, uint32_t shard_index,
+                    uint32_t shard_count, uint32_t local_tiles, bool tie_high, const uint32_t* bidx,
+                    const rt_bentry_t* blist, uint64_t entries, const rt_vtri_t* vgeom,
+                    std::vector<uint32_t>* btidx, std::vector<rt_bentry_t>* btrim, uint64_t* kept,
+                    uint32_t* blocks) {
+  btrim->assign(blist, blist + entries + RT_BLIST_PAD);
+  btidx->assign(2 * (size_t)local_tiles * 16u, 0u);
+  *kept = 0;
+  *blocks = 0;
+  std::vector<uint8_t> wins;
+  for (uint32_t lb = 0; lb < local_tiles * 16u; ++lb) {
+    const uint32_t first = bidx[2 * lb], count = bidx[2 * lb + 1];
+    const uint32_t gt = shard_index + (lb >> 4) * shard_count, blk = lb & 15u;
+    const uint32_t x0 = (gt % tiles_x) * 32u + (blk & 3u) * 8u, y0 = (gt / tiles_x) * 32u + (blk >> 2) * 8u;
+    wins.assign(count, 0);
+    for (uint32_t p = 0; p < 64u; ++p) {
+      const uint32_t px = x0 + (p & 7u), py = y0 + (p >> 3);
+      if (px >= width || py >= height) continue;  // edge tiles overhang the image
+      // rt_trace.h vis_test over the whole list; (bz, bpid) start at the cleared depth buffer
+      uint32_t bz = VX_OM_DEPTH_MASK;
+      int32_t bpid = -1, best = -1;
+      for (uint32_t i = 0; i < count; ++i) {
+        const rt_vtri_t& t = vgeom[blist[first + i].k];
+        if (!RectIn(t.rx, px) || !RectIn(t.ry, py) || t.zmin > bz) continue;
+        const int32_t E0 = EdgeEval(t.edges, px, py), E1 = EdgeEval(t.edges + 3, px, py),
+                      E2 = EdgeEval(t.edges + 6, px, py);
+        if (E0 < 0 || E1 < 0 || E2 < 0) continue;
+        const uint32_t z = VisDepth(E0, E1, E2, t.z);
+        if (z < bz || (z == bz && (tie_high ? t.pid > bpid : (bpid >= 0 && t.pid < bpid)))) {
+          bz = z;
+          bpid = t.pid;
+          best = (int32_t)i;
+        }
+      }
+      if (best >= 0) wins[best] = 1;
+    }
+    uint32_t n = 0;
+    for (uint32_t i = 0; i < count; ++i)
+      if (wins[i]) (*btrim)[first + n++] = blist[first + i];
+    (*btidx)[2 * lb] = first;
+    (*btidx)[2 * lb + 1] = n;
+    *kept += n;
+    *blocks += n ? 1u : 0u;
+  }
+}
+
 }  // namespace rt

@@ -11,6 +11,7 @@
 #pragma once
 
 #include <cstdint>
+#include <vector>
 
 #include "VX_types.h"
 #include "../kernels/rt_common.h"
@@ -60,5 +61,20 @@ std::vector<rt_cdesc_t> ChunkDescs(uint32_t width, uint32_t tiles_x, uint32_t sh
 std::vector<rt_bglayer_t> BgLayers(uint32_t width, uint32_t height, uint32_t tiles_x, uint32_t local_tiles,
                                    const uint32_t* order, uint32_t first_chunk, const rt_vtri_t* layers,
                                    uint32_t num_layers, const rt_prim_t* prims, uint32_t num_prims);
+
+// The block lists trimmed to their winners (kernels/setup_common.h rt_btrim_arg_t;
+// kernels/rt_btrim_kernel.hip builds them on the device), restated on the host: for every local
+// 8x8 block of the shard, each of its pixels inside the image is resolved over the block's whole
+// list by the frames' per-pixel test (rt_trace.h vis_test: covered rectangle, the three edge
+// values, the shader's depth word, vis_better under the scene's tie rule), and the entries whose
+// primitive wins a pixel are compacted to the front of the list's slots, unchanged and in order.
+// `bidx` (first, count per local block), `blist` (entries + RT_BLIST_PAD) and `vgeom` as the setup
+// left them.  *btrim: blist's copy with the kept entries moved up; *btidx: (bidx's first, the kept
+// count) per block; *kept / *blocks: the kept entries in total, the blocks that keep any.
+void TrimBlockLists(uint32_t width, uint32_t height, uint32_t tiles_x, uint32_t shard_index,
+                    uint32_t shard_count, uint32_t local_tiles, bool tie_high, const uint32_t* bidx,
+                    const rt_bentry_t* blist, uint64_t entries, const rt_vtri_t* vgeom,
+                    std::vector<uint32_t>* btidx, std::vector<rt_bentry_t>* btrim, uint64_t* kept,
+                    uint32_t* blocks);
 
 }  // namespace rt

@@ -175,3 +175,22 @@ typedef struct {
   uint32_t bgl_first;      // the first background chunk, as an index into the chunk table
   uint64_t bgl_addr;       // rt_bglayer_t [bgl_n]
 } rt_setup_arg_t;
+
+// The trimmed block lists (rt_btrim_kernel.hip; app/setup.cpp TrimBlockLists restates them): per
+// local 8x8 block, the entries of its candidate list whose primitive wins at least one of the
+// block's pixels inside the image, compacted to the front of the list's own slots in their order,
+// each with its rectangle and bound words as they were (supersets for the kept suffix: the scan's
+// early out stays conservative); the slots behind them keep the list's entries, so every slot a
+// scan loads ahead names a geometry record.  The launch's argument buffer is a copy of the render
+// arguments with the whole-block task map over every local block (no work order, no split tiles,
+// num_tasks = blocks * 64) and the untrimmed lists, and this area behind it.
+typedef struct {
+  uint64_t btrim_addr;     // rt_bentry_t [entries + RT_BLIST_PAD]: the trimmed lists, at blist's offsets
+  uint64_t btidx_addr;     // uint32[2] per local block: bidx's offset, the kept count
+  uint64_t stat_addr;      // u32 [2]: kept entries in total, blocks that keep any (zeroed by the host)
+  uint32_t entries;        // blist's entries (the padding entries follow them)
+  uint32_t pad;
+  uint32_t stat[2];        // (stat_addr points here)
+  uint32_t pad2[2];
+} rt_btrim_arg_t;
+#define RT_BTRIM_ARG_OFFSET sizeof(rt_kernel_arg_t)

@@ -39,7 +39,9 @@ RECORDS = {"prims": (0, np.int32, 32), "bbox": (1, np.uint32, 2), "vis": (2, np.
            "cdesc": (14, np.uint32, 4), "cdesc_host": (15, np.uint32, 4),
            "sidx": (12, np.uint32, 2), "slist": (13, np.float32, 12),
            "oidx": (16, np.uint32, 2), "olist": (17, np.uint32, 1),
-           "bglayer": (18, np.uint32, 2), "bglayer_host": (19, np.uint32, 2)}
+           "bglayer": (18, np.uint32, 2), "bglayer_host": (19, np.uint32, 2),
+           "btidx": (20, np.uint32, 2), "btrim": (21, np.uint32, 4),
+           "btidx_host": (22, np.uint32, 2), "btrim_host": (23, np.uint32, 4)}
 RT_BVH_STACK4_UNUSED = 0xFFFFFFFF
 RT_BVH_BUILD_HOST = 2
 CLEAR_COLOR = 0xFF000000               # draw3d/main.cpp:47
@@ -71,7 +73,8 @@ class SetupStats(C.Structure):
                 ("blist_entries", C.c_uint64), ("blist_max", C.c_uint32), ("slist_on", C.c_uint32),
                 ("slist_entries", C.c_uint64), ("path_queue", C.c_uint32), ("slist_built", C.c_uint32),
                 ("slist_stale", C.c_uint32), ("lane_grid", C.c_uint32),
-                ("bg_first_chunk", C.c_uint32), ("tier_groups", C.c_uint32)]
+                ("bg_first_chunk", C.c_uint32), ("tier_groups", C.c_uint32),
+                ("btrim_entries", C.c_uint64), ("btrim_blocks", C.c_uint32), ("pad", C.c_uint32)]
 
     def as_dict(self):
         return {n: getattr(self, n) for n, _ in self._fields_ if n != "pad"}
@@ -159,6 +162,7 @@ def lib():
             "rt_scene_setup_prims": [vp, u32, u32, vp, u64],
             "rt_scene_setup_vis": [vp, u32, u32, vp, u64],
             "rt_scene_bg_layers": [vp, u32, u32, vp, u32, vp, u64, C.POINTER(u64)],
+            "rt_scene_block_trim": [vp, u32, u32, u32, u32, vp, vp, vp, vp, C.POINTER(u64), C.POINTER(u64)],
             "rt_scene_vis_tree": [vp, u32, u32, C.c_float, vp, C.POINTER(u32), vp, C.POINTER(u32),
                                   C.POINTER(u32)],
             "rt_framebuffer_device": [vp, C.POINTER(vp), C.POINTER(u64)],
@@ -306,6 +310,21 @@ class Scene:
                                         first_chunk, out.ctypes.data, tiles * 16, C.byref(n)),
                "rt_scene_bg_layers")
         return out[:n.value]
+
+    def block_trim(self, width: int, height: int, shard_index: int = 0, shard_count: int = 1):
+        """The per-block candidate lists of a width x height frame (one shard) and the same lists
+        trimmed to the entries whose primitive wins a pixel of the block, computed on the host:
+        (bidx uint32[blocks, 2], blist uint32[entries + 3, 4], btidx, btrim) -- btidx keeps bidx's
+        first entry beside the kept count, btrim the kept entries at the front of each list's slots."""
+        ne, nb = C.c_uint64(), C.c_uint64()
+        _check(lib().rt_scene_block_trim(self._h, width, height, shard_index, shard_count, None, None, None, None,
+                                         C.byref(ne), C.byref(nb)), "rt_scene_block_trim")
+        bidx, btidx = (np.zeros((max(nb.value, 1), 2), np.uint32) for _ in range(2))
+        blist, btrim = (np.zeros((ne.value + 3, 4), np.uint32) for _ in range(2))
+        _check(lib().rt_scene_block_trim(self._h, width, height, shard_index, shard_count, bidx.ctypes.data,
+                                         blist.ctypes.data, btidx.ctypes.data, btrim.ctypes.data, C.byref(ne),
+                                         C.byref(nb)), "rt_scene_block_trim")
+        return bidx[:nb.value], blist, btidx[:nb.value], btrim
 
     def setup_vis(self, width: int, height: int) -> np.ndarray:
         """Primary-visibility records (uint32[P, 3]: covered-pixel rectangle
@@ -469,7 +488,9 @@ class Renderer:
         """One per-resolution record array of the current configuration
         (RECORDS: prims, bbox, vis, vnodes, vtris, vlayers, vgeom, order,
         ptris, geom, bidx, blist -- the per-block candidate lists, blist with
-        its 3 padding entries; oidx, olist -- the ordered tail's per-block
+        its 3 padding entries; btidx, btrim -- the same lists trimmed to their
+        winners, which the frames scan, and btidx_host, btrim_host, their host
+        restatement; oidx, olist -- the ordered tail's per-block
         lists, olist with its 2 padding entries), as [count, words]."""
         which, dt, words = RECORDS[name]
         n = C.c_uint64()
