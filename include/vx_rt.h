@@ -368,7 +368,9 @@ typedef struct {
   uint64_t btrim_entries; /* the trimmed block lists (RT_REC_BTRIM) the frames scan: the entries kept --
                              0: no trim (no lists, RT_RENDER_INSTRUMENTED, env RT_BLIST_TRIM=0) */
   uint32_t btrim_blocks;  /* ... and the blocks that keep any */
-  uint32_t pad;
+  uint32_t fused_chunk;   /* 1: the frames carry RT_FLAG_FUSED -- image rt_kernel traces a wave's last
+                             geometry chunk's shadow rays in place while the lists hold (env
+                             RT_FUSED_CHUNK=0 at configure: 0) */
 } rt_setup_stats_t;
 /* (reads back the status of shadow lists queued by rt_renderer_set_light:
  * waits for the device) */

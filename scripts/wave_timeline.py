@@ -86,7 +86,12 @@ def main():
                              "lane_visits_avg": float(irows[slow, 7].mean()) / 64,
                              "lane_tri_tests_avg": float(irows[slow, 8].mean()) / 64})
     if not path:  # phase stamps (RT_STAMPS rt_kernel): 3 before primary, 14 primary done,
-        # 4 layers done, 11 shaded, 5 queued/stored, 6 non-final drain start, 15 final drain
+        # 4 layers done, 11 shaded, 5 queued/stored, 6 non-final drain start, 15 final drain.
+        # A chunk traced in place (RT_FUSED_CHUNK, the stamp image has it; env RT_FUSED_CHUNK=0 for
+        # the queue's timeline): "shade" then holds the plane arithmetic and the cell header's issue,
+        # "plane_queue" is the list scan in place and the store, and the final drain finds no ray
+        # (final_drain_rays 0: what is left of "final_drain" is the empty queue's look and the
+        # wave's counter flush)
         ph = lambda a, b: float((rows[slow, b] - rows[slow, a]).mean()) / 100  # noqa: E731
         out["slowest50"]["phases_us"] = {
             "to_primary": ph(12, 3), "primary": ph(3, 14), "layers": ph(14, 4), "shade": ph(4, 11),

@@ -26,6 +26,7 @@
 #include "bvh.h"
 #include "bvh_common.h"
 #include "cgltrace.h"
+#include "fused_chunk.h"
 #include "rt_internal.h"
 #include "sah_common.h"
 #include "setup_common.h"
@@ -555,6 +556,7 @@ int rt_renderer_setup_stats(rt_renderer_h r, rt_setup_stats_t* st) {
   }
   r->setup.slist_on = r->arg.slist_on;
   r->setup.slist_stale = r->sl_stale ? 1u : 0u;
+  r->setup.fused_chunk = (r->arg.flags & RT_FLAG_FUSED) ? 1u : 0u;
   r->setup.lane_grid = lane_grid_of(r);
   r->setup.bg_first_chunk = r->bg_ok ? r->bg_first : 0u;
   {
@@ -1452,7 +1454,11 @@ int rt_renderer_configure(rt_renderer_h r, const rt_render_params_t* p) {
             (s->tie_high ? RT_FLAG_TIE_HIGH : 0u) | (compact ? RT_FLAG_COMPACT : 0u) |
             (use_bvh4 ? RT_FLAG_BVH4 : 0u) |
             // binary16 node records: the host tree's, or the device tree's (BVHB_HALF)
-            (use_bvh4 && (r->gpu_bvh || !s->bvh.nodes4h.empty()) ? RT_FLAG_BVH4H : 0u);
+            (use_bvh4 && (r->gpu_bvh || !s->bvh.nodes4h.empty()) ? RT_FLAG_BVH4H : 0u) |
+            // rt_kernel's in-place last chunk (env RT_FUSED_CHUNK, read here)
+            rtfused::flag({(p->flags & RT_RENDER_SHADOWS) != 0, (p->flags & RT_RENDER_PATH) != 0,
+                           (p->flags & RT_RENDER_FLAT) != 0, raster, tail},
+                          std::getenv("RT_FUSED_CHUNK"), RT_FLAG_FUSED);
   // the regular RT / PT images walk only the binary16 BVH4 (RT_ONLY_BVH4H);
   // any other layout runs the generic images (the deep ones: every layout,
   // 32-entry stack)

@@ -56,6 +56,10 @@
 #define RT_FLAG_BVH4     0x40u   // traverse the 4-wide BVH (nodes4) instead of the BVH2
 #define RT_FLAG_BVH4H    0x80u   // BVH4 node steps read the binary16 rt_node4h_t form
 #define RT_FLAG_COVERAGE 0x100u  // raster mode: covered pixels white, no shading / OM
+// primary+shadow frames of image rt_kernel: a wave traces its last geometry chunk's shadow rays in
+// place behind the shading's loads (rt_kernel.hip RT_FUSED_CHUNK; app/fused_chunk.h sets it at
+// configure, env RT_FUSED_CHUNK=0: off).  Every other image ignores the bit.
+#define RT_FLAG_FUSED    0x200u
 
 // a render launch's words (vortex_hip.h vx_hip_set_launch_words, vx_spawn.h
 // vx_launch_words; rt_render_start sets them on every frame): w[0..2] the

@@ -69,6 +69,14 @@
 #else
 #define RT_BG_TABLE 0
 #endif
+// 1 (RT_KERNEL_IMG_DEFS: rt_kernel and its A/B variants; the stamp image): under RT_FLAG_FUSED a wave
+// traces its last chunk's shadow rays in place, around its shading's loads (fused_planes / fused_header / fused_verdict below)
+#ifndef RT_FUSED_CHUNK
+#define RT_FUSED_CHUNK 0
+#endif
+#if RT_FUSED_CHUNK && (RT_LIGHTS || RT_PATHQ || RT_BVH_WALK || !RT_ONLY_BVH4H)
+#error "RT_FUSED_CHUNK is for the one-light primary+shadow list image on the binary16 BVH4"
+#endif
 #if RT_LIGHTS && (RT_PATHQ || RT_BVH_WALK || !RT_ONLY_BVH4H)
 #error "RT_LIGHTS is for the primary+shadow list image on the binary16 BVH4"
 #endif
@@ -104,8 +112,125 @@ struct WaveLds {
   uint32_t q_count;
 };
 
+#if RT_FUSED_CHUNK
+// vx_spawn_chunks_ex (vx_spawn.h) over the chunks [0, c1), handing kernel_func each chunk's place
+// in the wave's deal: the wave takes every nw-th chunk, so chunk c is its last when c + nw >= c1.
+// From the loop's own registers: nothing is read and nothing more is held across the chunks.
+struct ChunkPlace {
+  bool last;
+};
+template <typename F, typename E, typename Arg>
+__device__ __forceinline__ int spawn_chunks_placed(uint32_t num_tasks, uint32_t c1, uint32_t w, uint32_t nw,
+                                                   F kernel_func, E epilogue, Arg* arg) {
+  __vx_declare_tasks(num_tasks);
+  const uint32_t nchunks = (num_tasks + VX_CHUNK - 1) / VX_CHUNK;
+  if (c1 > nchunks) c1 = nchunks;
+  uint32_t ran = 0;
+  vx_task_t task;
+  task.threadIdx.x = task.threadIdx.y = task.threadIdx.z = 0;
+  task.blockIdx.y = task.blockIdx.z = 0;
+  // (the wave's index as a scalar: the chunk loop is a scalar loop and a chunk's place a scalar
+  // compare, no lane mask kept across the body)
+  for (uint32_t c = (uint32_t)__builtin_amdgcn_readfirstlane(w); c < c1; c += nw) {
+    const uint32_t t = c * VX_CHUNK + (threadIdx.x & 63u);
+    if (t < num_tasks) {
+      task.task_id = t;
+      task.blockIdx.x = t;
+      ChunkPlace cp;
+      cp.last = c + nw >= c1;
+      kernel_func(task, cp, arg);
+      ++ran;
+    }
+    // (behind the wave's last chunk the final drain below is this one and more: the same rounds)
+    if (c + nw < c1) epilogue(false, arg);
+  }
+  epilogue(true, arg);
+  vx_mpm_add(VX_MPM_TASKS, ran);
+  return 0;
+}
+
+// A wave's last chunk with the light-space lists on: from block_primary's
+// winners on, the colour (layers, primitive record, drawcall record, texels) and the shadow
+// verdict (plane record, cell header, list records) do not depend on each other, and the chunk's
+// rays go nowhere but through this wave -- so kernel_body traces them in place, per lane, their
+// loads issued around the shading's instead of after a trip through the LDS queue:
+//   fused_planes  the winners' plane records, issued before the layer loop;
+//   fused_header  behind the layers: th, the shadow ray and its cell from the Ray and x, y the wave
+//                 holds, and the cell header (off, n: one 8-byte load) issued ahead of shade_wave's
+//                 records and taps.  Vector loads return in order: the wait for the taps covers it;
+//   fused_verdict behind the shade: the scan as occluded_list runs it (slist_scan) and the pixel's
+//                 one store.
+// The layers and the shade are kernel_body's own, one copy for both ways through a chunk (a second
+// copy of them for this path: 32 SGPR spills against the parent's 26).  Across the shade a lane
+// keeps its segment and the header, eight VGPRs.  Pixels and the ray counters are those of
+// kernel_body + shadow_drain.
+struct FusedRay {
+  float o[3], d[3];  // the shadow segment (shadow_ray)
+  uint2 hd;          // its cell's off, n; n = 0: no ray, or an empty cell -- nothing to scan
+};
+struct PlaneRec {
+  float4 a, b, c;
+};
+__device__ __forceinline__ PlaneRec fused_planes(const Scene& S, int32_t hit) {
+  PlaneRec P;
+  P.a = P.b = P.c = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+  if (hit >= 0) {
+    const uint32_t o = S.ptris + 48u * (uint32_t)hit;
+    P.a = S.A.ld_f4(o);
+    P.b = S.A.ld_f4(o + 16);
+    P.c = S.A.ld_f4(o + 32);
+  }
+  return P;
+}
+__device__ __forceinline__ FusedRay fused_header(const Scene& S, uint32_t x, uint32_t y, int32_t hit,
+                                                 const PlaneRec& P, Counters& cnt) {
+  FusedRay f;
+  Ray r, s;
+  primary_dir(S, x, y, r);
+  const float th = hit >= 0 ? plane_t(r, P.a, P.b, P.c) : 0.0f;
+  const bool shadow = hit >= 0 && secondary_ok(th);
+  shadow_ray(S, r, th, s);
+  f.hd = make_uint2(0u, 0u);
+  if (shadow) f.hd = S.A.ld_u2(S.sidx + 8u * slist_cell(s, S.slist_n));
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    f.o[k] = s.o[k];
+    f.d[k] = s.d[k];
+  }
+  cnt.shadow += shadow;
+  return f;
+}
+__device__ __forceinline__ void fused_verdict(const Scene& S, uint32_t x, uint32_t y, uint32_t out, bool in,
+                                              int32_t hit, FusedRay f, uint32_t color, Counters& cnt) {
+  if (f.hd.y != 0u) {
+    Ray s;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      s.o[k] = f.o[k];
+      s.d[k] = f.d[k];
+    }
+    if (slist_scan(S, s, hit, cnt, S.slist, f.hd.x, f.hd.y)) {
+      ++cnt.occluded;
+      color = shadowed(color);
+    }
+  }
+  if (in) store_out(S, out, color);
+}
+#endif
+
+#if RT_FUSED_CHUNK
+// (cp: the chunk's place in the wave's deal)
+#define RT_BODY_DEAL , const ChunkPlace &cp
+// (a wave-uniform word of the body tested where it stands, rt_usgpr: hoisted out of the chunk loop and
+// kept as lane masks, these tests were SGPR spills the image with the fused path has no room for;
+// the other images keep their code)
+#define RT_BODY_U(v) rt_usgpr(v)
+#else
+#define RT_BODY_DEAL
+#define RT_BODY_U(v) (v)
+#endif
 __device__ __forceinline__ void kernel_body(const vx_task_t& task, const Scene& S, WaveLds& w,
-                                            Counters& cnt) {
+                                            Counters& cnt RT_BODY_DEAL) {
   const uint32_t t = task.blockIdx.x;
   // the chunk's task map in scalar registers (every lane runs the same chunk)
   const uint32_t c = (uint32_t)__builtin_amdgcn_readfirstlane(t) >> 6;
@@ -115,7 +240,7 @@ __device__ __forceinline__ void kernel_body(const vx_task_t& task, const Scene& 
   // block's origin, lane 0's framebuffer word and the list header in one
   // scalar load; other tiers, or no table: chunk_map and the bidx load
   uint2 oc = make_uint2(0u, 0u);
-  if (S.cdesc != 0 && c >= S.cdesc_first) {
+  if (RT_BODY_U(S.cdesc) != 0 && c >= S.cdesc_first) {
     const uint4 d = S.A.sld_u4(S.cdesc + 16u * (c - S.cdesc_first));
     uint32_t ln = t & 63u;
     asm volatile("" : "+v"(ln));  // worked out here: hoisted out of the chunk loop its parts spill
@@ -130,7 +255,7 @@ __device__ __forceinline__ void kernel_body(const vx_task_t& task, const Scene& 
     x = cx;
     y = cy;
     out = co;
-    if (S.blist_blocks) oc = block_header(S, (cm.lt << 4) | cm.blk);
+    if (RT_BODY_U(S.blist_blocks)) oc = block_header(S, (cm.lt << 4) | cm.blk);
   }
 #else
   const ChunkMap cm = chunk_map(S, task_args(S), c);
@@ -139,14 +264,14 @@ __device__ __forceinline__ void kernel_body(const vx_task_t& task, const Scene& 
 #endif
   const bool in = x < S.width && y < S.height;  // edge tiles overhang the image
   cnt.primary += in;
-  const bool tie_high = (S.flags & RT_FLAG_TIE_HIGH) != 0;
+  const bool tie_high = (RT_BODY_U(S.flags) & RT_FLAG_TIE_HIGH) != 0;
 #ifdef RT_STAMPS
   if (lane_id() == 0) __vx_mpm_lds[3] = (uint32_t)__builtin_amdgcn_s_memrealtime();
 #endif
   // primary visibility: the raster's winner at this pixel
 #if RT_CHUNK_DESC && !RT_BVH_WALK
   int32_t hit;
-  if (S.blist_blocks) {
+  if (RT_BODY_U(S.blist_blocks)) {
     hit = block_primary(S, oc, x, y, in, tie_high, cnt);
   } else {  // no lists: the packet walk of the tree (trace_primary)
     const int32_t h = trace_primary_packet(walk_scene(S), x, y, in, tie_high, cnt);
@@ -159,13 +284,35 @@ __device__ __forceinline__ void kernel_body(const vx_task_t& task, const Scene& 
   if (lane_id() == 0) __vx_mpm_lds[14] = (uint32_t)__builtin_amdgcn_s_memrealtime();
 #endif
   cnt.hits += hit >= 0;
+#if RT_FUSED_CHUNK
+  // wave-uniform: the frame's flag and shadows, lists that hold for this frame's light (load_scene
+  // clears slist_on under RT_LW_NO_SLIST), the wave's last chunk; an earlier chunk's rays, still
+  // queued, are drained behind it as ever
+  const bool fused = (rt_usgpr(S.flags) & (RT_FLAG_FUSED | RT_FLAG_SHADOWS)) == (RT_FLAG_FUSED | RT_FLAG_SHADOWS) &&
+                     rt_usgpr(S.slist_on) && cp.last;
+  PlaneRec P;
+  if (fused) P = fused_planes(S, hit);
+#endif
   const int32_t spid = resolve_layers(S, x, y, in && hit < 0, hit, cnt);
 #ifdef RT_STAMPS
   if (lane_id() == 0) __vx_mpm_lds[4] = (uint32_t)__builtin_amdgcn_s_memrealtime();
 #endif
+#if RT_FUSED_CHUNK
+  FusedRay fr;
+  if (fused) fr = fused_header(S, x, y, hit, P, cnt);
+#endif
   uint32_t color = shade_wave(S, spid, x, y, S.clear_color, cnt);
 #ifdef RT_STAMPS
   if (lane_id() == 0) __vx_mpm_lds[11] = (uint32_t)__builtin_amdgcn_s_memrealtime();
+#endif
+#if RT_FUSED_CHUNK
+  if (fused) {
+    fused_verdict(S, x, y, out, in, hit, fr, color, cnt);
+#ifdef RT_STAMPS
+    if (lane_id() == 0) __vx_mpm_lds[5] = (uint32_t)__builtin_amdgcn_s_memrealtime();
+#endif
+    return;
+  }
 #endif
   Ray r;
   primary_dir(S, x, y, r);
@@ -437,6 +584,20 @@ VX_MAIN(rt_kernel_arg_t, arg, RT_BLOCK_THREADS) {
   // bg_first_chunk; tag 0: the grid's waves share every chunk, vx_spawn_tasks_ex's deal
   const uint32_t tier_wgs = vx_launch_tag != 0 ? vx_launch_tag : gridDim.x;
   const uint32_t tier_end = vx_launch_tag != 0 ? bg_first_chunk(arg) : 0xffffffffu;
+#endif
+#if RT_FUSED_CHUNK
+  // the same deals, each chunk with its place in the wave's
+#if RT_BG_TIER
+  const uint32_t deal_w = blockIdx.x * kWaves + (threadIdx.x >> 6), deal_nw = tier_wgs * kWaves, deal_end = tier_end;
+#else
+  const uint32_t deal_w = __vx_logical_block() * kWaves + (threadIdx.x >> 6), deal_nw = gridDim.x * kWaves,
+                 deal_end = 0xffffffffu;
+#endif
+  const int rc = spawn_chunks_placed(
+      S.num_tasks, deal_end, deal_w, deal_nw,
+      [&](const vx_task_t& task, const ChunkPlace& cp, const Scene* s) { kernel_body(task, *s, w, cnt, cp); },
+      [&](bool final, const Scene* s) { shadow_drain(final, *s, w, cnt); }, &S);
+#elif RT_BG_TIER
   const int rc = vx_spawn_chunks_ex(
       S.num_tasks, 0u, tier_end, blockIdx.x * kWaves + (threadIdx.x >> 6), tier_wgs * kWaves,
       [&](const vx_task_t& task, const Scene* s) { kernel_body(task, *s, w, cnt); },

@@ -850,11 +850,10 @@ __device__ __forceinline__ float slist_limit(const Ray& s) {
 }
 // (the lists of one light: their index and entries, at slist_n cells per face side -- a light of
 // the table behind the argument block, or, the overload below, the scene's own)
-__device__ __forceinline__ bool occluded_list(const Scene& S, const Ray& s, bool act, int32_t skip,
-                                              Counters& cnt, uint32_t sidx, uint32_t slist, uint32_t slist_n) {
-  if (!act) return false;
-  const uint32_t cell = slist_cell(s, slist_n);
-  const uint32_t off = S.A.ld_u32(sidx + 8u * cell), n = S.A.ld_u32(sidx + 8u * cell + 4u);
+// (the scan of a cell's n records from record `off` on: occluded_list's second half, and
+// rt_kernel.hip's fused chunk behind a header it loaded itself)
+__device__ __forceinline__ bool slist_scan(const Scene& S, const Ray& s, int32_t skip, Counters& cnt,
+                                           uint32_t slist, uint32_t off, uint32_t n) {
   const float lim = slist_limit(s);
   uint32_t o = slist + 48u * off;
   for (uint32_t q = 0; q < n; q += 2, o += 96u) {
@@ -873,6 +872,13 @@ __device__ __forceinline__ bool occluded_list(const Scene& S, const Ray& s, bool
     }
   }
   return false;
+}
+__device__ __forceinline__ bool occluded_list(const Scene& S, const Ray& s, bool act, int32_t skip,
+                                              Counters& cnt, uint32_t sidx, uint32_t slist, uint32_t slist_n) {
+  if (!act) return false;
+  const uint32_t cell = slist_cell(s, slist_n);
+  const uint32_t off = S.A.ld_u32(sidx + 8u * cell), n = S.A.ld_u32(sidx + 8u * cell + 4u);
+  return slist_scan(S, s, skip, cnt, slist, off, n);
 }
 __device__ __forceinline__ bool occluded_list(const Scene& S, const Ray& s, bool act, int32_t skip,
                                               Counters& cnt) {
@@ -1604,9 +1610,8 @@ __device__ __forceinline__ int32_t trace_primary(const Scene& S, uint32_t lb, ui
 // triangle `pid` (rt_tri_t by pid in ptris): MT's t without the coverage
 // test (mt_hit's operations); the origin of the shadow ray / path.  Not
 // finite or <= 0 (a plane edge-on to the ray): no secondary rays.
-__device__ __forceinline__ float plane_t(const Scene& S, const Ray& r, int32_t pid) {
-  const uint32_t o = S.ptris + 48u * (uint32_t)pid;
-  const float4 a = S.A.ld_f4(o), b = S.A.ld_f4(o + 16), c = S.A.ld_f4(o + 32);
+// (from the record's three words, for a caller that loaded them itself)
+__device__ __forceinline__ float plane_t(const Ray& r, const float4& a, const float4& b, const float4& c) {
   const float e1[3] = {b.x, b.y, b.z}, e2[3] = {c.x, c.y, c.z};
   float pvec[3], tvec[3], qvec[3];
   cross3(pvec, r.d, e2);
@@ -1616,6 +1621,10 @@ __device__ __forceinline__ float plane_t(const Scene& S, const Ray& r, int32_t p
   tvec[2] = r.o[2] - a.z;
   cross3(qvec, tvec, e1);
   return dot3(e2, qvec) / det;
+}
+__device__ __forceinline__ float plane_t(const Scene& S, const Ray& r, int32_t pid) {
+  const uint32_t o = S.ptris + 48u * (uint32_t)pid;
+  return plane_t(r, S.A.ld_f4(o), S.A.ld_f4(o + 16), S.A.ld_f4(o + 32));
 }
 __device__ __forceinline__ bool secondary_ok(float t) { return t > 0.0f && t < INFINITY; }
 

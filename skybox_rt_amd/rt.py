@@ -74,7 +74,7 @@ class SetupStats(C.Structure):
                 ("slist_entries", C.c_uint64), ("path_queue", C.c_uint32), ("slist_built", C.c_uint32),
                 ("slist_stale", C.c_uint32), ("lane_grid", C.c_uint32),
                 ("bg_first_chunk", C.c_uint32), ("tier_groups", C.c_uint32),
-                ("btrim_entries", C.c_uint64), ("btrim_blocks", C.c_uint32), ("pad", C.c_uint32)]
+                ("btrim_entries", C.c_uint64), ("btrim_blocks", C.c_uint32), ("fused_chunk", C.c_uint32)]
 
     def as_dict(self):
         return {n: getattr(self, n) for n, _ in self._fields_ if n != "pad"}
