@@ -711,6 +711,81 @@ int rt_read_denoise_guide(rt_renderer_h r, rt_denoise_guide_t* guide, uint32_t* 
  * NO REFERENCE. */
 int rt_write_accum(rt_renderer_h r, const uint32_t* rec, uint64_t count, uint32_t n);
 
+/* Ambient occlusion on the device from a frame's visibility records.  NO
+ * REFERENCE (the definition below composes the path tracer's own pinned
+ * routines; tests/ao_reference.py restates it from the oracle's primitives and
+ * the device is held to that bit for bit).
+ *
+ * Framebuffer.  Linear W x H only; pixel p = y * W + x; rec[p] is the rt_aov_t
+ * the last rt_render_aov / rt_relight_capture since rt_renderer_configure
+ * wrote.
+ * Ray pixel.  (depth_flags & RT_AOV_GEOM) and t > 0 && t < +inf.  This does not
+ * depend on RT_RENDER_SHADOWS (RT_AOV_SHADOW_RAY is not read).
+ * A ray pixel's rays -- the path tracer's first vertex, op for op, in binary32:
+ *   d = the pixel's primary direction ((x + 0.5) * 2 / W - 1, (y + 0.5) * 2 / H
+ *   - 1, 1); P = d * (t * 0.999755859375f); n = tri_normal(e1, e2 of pid's
+ *   RT_REC_PTRIS record, d) (kernels/rt_path.h); sample c -- the 0-based cursor
+ *   since rt_renderer_ao_begin or rt_renderer_ao_reset -- has direction
+ *   bounce_dir(n, pt_key(seed + c mod 2^32, p, 0)).  The sample is occluded iff
+ *   some geometry triangle other than pid meets the ray (Moeller-Trumbore as the
+ *   frames' rays, tmin = 0) at t < radius; radius is a positive float or +inf.
+ *   The verdict does not depend on traversal order.
+ * Record.  One uint32 per framebuffer pixel: the occluded samples so far; 0 for
+ * a pixel that is not a ray pixel.  N, the sample cursor, is the renderer's.
+ * Resolve.  rt_ao_resolve(argb, o, N) keeps the alpha byte and returns per
+ * colour channel c (2 * c * (N - o) + N) / (2 * N) in integer division; argb
+ * when N = 0.  N <= 65535.
+ *
+ * rt_renderer_ao_begin(r, params): valid where rt_render_aov_start is, with a
+ * linear framebuffer and after a record launch: -2 (rt_last_error says why) for
+ * everything rt_render_aov_start refuses, for RT_RENDER_COMPACT or shards, when
+ * no record launch ran since the last configure, for a radius that is NaN or
+ * not positive.  It allocates the count buffer (W * H * 4 B; rt_renderer_
+ * configure and rt_renderer_free release it and end the session) and loads
+ * rt_ao.vxbin and rt_ao_resolve.vxbin (the kernel directory's, else the
+ * library's) on the first call; the next tracing launch resets.
+ * rt_renderer_ao_reset: the cursor back to 0, the next launch resets -- no
+ * clearing launch and no copy, the reset travels in the launch words.
+ * rt_renderer_set_light / rt_renderer_set_lights do not end the session: pid
+ * and t do not depend on lights.
+ *
+ * rt_render_ao_start(r, samples): one launch of rt_ao (kernels/
+ * rt_ao_kernel.hip) tracing samples = 1..64 rays per ray pixel, with no host
+ * wait and no copy; -2 for samples out of range or a cursor that would pass
+ * 65535.  An ordinary launch as a record launch is: no lane, behind the frames
+ * in flight.  It writes only the counts -- neither the framebuffer nor the
+ * visibility records -- rt_render_wait covers it, and with RT_RENDER_COUNTERS
+ * rt_render_stats after it gives shadow_rays = the rays traced and occluded =
+ * the sum of their verdicts (every other counter 0).
+ *
+ * rt_render_ao_resolve_start(r, mode, weights, n): one launch of rt_ao_resolve
+ * (kernels/rt_ao_resolve_kernel.hip), a streaming pass into the framebuffer in
+ * use, as a relight launch goes.  RT_AO_GREY writes rt_ao_resolve(0xffffffff,
+ * o, N); weights and n are ignored.  RT_AO_MODULATE writes rt_ao_resolve(
+ * rt_relight_resolve(base, depth_flags, light_mask, weights, n), o, N), the
+ * relit pixel times the ambient term; with weights NULL the colour is the base
+ * colour itself.  -2 for N = 0, for an unknown mode, for RT_AO_MODULATE without
+ * a live relight capture (rt_render_relight_start's rule), with n not the
+ * capture's light count or with every weight 0. */
+typedef struct {
+  float    radius;   /* > 0, or +inf */
+  uint32_t seed;     /* sample c is keyed by seed + c */
+} rt_ao_params_t;
+#define RT_AO_DEFAULT_SEED 0x5EEDu   /* rtapp -K's, and the Python layer's default */
+#define RT_AO_GREY 0u
+#define RT_AO_MODULATE 1u
+int rt_renderer_ao_begin(rt_renderer_h r, const rt_ao_params_t* params);
+int rt_renderer_ao_reset(rt_renderer_h r);
+int rt_render_ao_start(rt_renderer_h r, uint32_t samples);
+int rt_render_ao(rt_renderer_h r, uint32_t samples);            /* start + wait */
+int rt_renderer_ao_samples(rt_renderer_h r, uint32_t* n);       /* the sample cursor N */
+/* the counts in framebuffer order, count >= the framebuffer's pixels (waits for the device) */
+int rt_read_ao(rt_renderer_h r, uint32_t* out, uint64_t count);
+int rt_render_ao_resolve_start(rt_renderer_h r, uint32_t mode, const uint8_t* weights, uint32_t n);
+int rt_render_ao_resolve(rt_renderer_h r, uint32_t mode, const uint8_t* weights, uint32_t n);  /* start + wait */
+/* the resolved pixel restated on the host (occluded above n counts as n) */
+uint32_t rt_ao_resolve(uint32_t argb, uint32_t occluded, uint32_t n);
+
 /* Read back one per-resolution record array of the current configuration
  * (layouts: kernels/rt_common.h; NO REFERENCE).  out NULL = size query
  * (*size = bytes). */

@@ -33,7 +33,8 @@ REQUIRED = ("libvortex.so", "libvortex-hip.so", "librtapp.so", "rtapp",
             "rt_om.vxbin", "pt_accum.vxbin", "rt_lights.vxbin", "rt_lights_stats.vxbin",
             "pt_lights.vxbin", "pt_lights_accum.vxbin", "tex_kat.vxbin", "rt_aov.vxbin",
             "rt_aov_base.vxbin", "rt_relight.vxbin", "rt_kat.vxbin", "rt_kat_pt.vxbin",
-            "rt_aov_guide.vxbin", "rt_denoise_prep.vxbin", "rt_denoise_pass.vxbin")
+            "rt_aov_guide.vxbin", "rt_denoise_prep.vxbin", "rt_denoise_pass.vxbin",
+            "rt_ao.vxbin", "rt_ao_resolve.vxbin")
 
 
 class NativeLibraryMissing(RuntimeError):

@@ -40,6 +40,12 @@
 // -L / -M -- after the frame a relight capture (rt_relight_capture) and one
 // relight launch under the weights (rt_render_relight), whose frame is the one
 // written to -o, and one line "Relight: <n> lights, weights w0,w1,...";
+// -K samples[,radius]: with -S, after the frame a relight capture and that many
+// ambient-occlusion samples per ray pixel (rt_render_ao: launches of 64, then
+// one for the rest; rays of at most `radius`, by default unbounded; seed
+// RT_AO_DEFAULT_SEED), then the modulate resolve (rt_render_ao_resolve) under
+// -W's weights, or unit weights -- the relit frame times the ambient term,
+// written to -o -- and one line "AO: <samples> samples, radius <r>";
 // multi-GPU (one process per GPU over
 // librt_shard.so / RCCL): -G rank,ranks -I idfile -- this process renders
 // 32x32 tiles t with t % ranks == rank, rank 0 writes the RCCL communicator
@@ -92,6 +98,7 @@ std::vector<std::array<float, 3>> more_lights;  // -M: lights beside the one of 
 const char* aov_file = nullptr;       // -V: write the frame's visibility records
 const char* weights_arg = nullptr;    // -W: relight the frame under these per-light weights
 const char* denoise_arg = nullptr;    // -D: with -A, denoise the accumulated frame
+const char* ao_arg = nullptr;         // -K: with -S, the frame times its ambient occlusion
 
 #ifdef RT_APP_RASTER
 const char* kOpts = "t:i:o:r:w:h:k:n:z?";
@@ -101,7 +108,7 @@ void usage() {
               "[-k tilelogsize] [-n repeat]\n");
 }
 #else
-const char* kOpts = "t:s:e:i:o:r:w:h:k:n:L:M:P:G:I:B:A:V:W:D:uxyzSRFHO?";
+const char* kOpts = "t:s:e:i:o:r:w:h:k:n:L:M:P:G:I:B:A:V:W:D:K:uxyzSRFHO?";
 void usage() {
   std::printf("Vortex 3D Rendering Test (MI355X).\n"
               "Usage: [-t trace] [-s startdraw] [-e enddraw] [-o output] [-r reference] [-w width] "
@@ -114,6 +121,7 @@ void usage() {
               "       [-D passes[,zs,ls]: with -A, write the accumulated frame through the edge-avoiding filter]\n"
               "       [-V file: the frame's per-pixel visibility records (primary + shadow frames)]\n"
               "       [-W w0,w1,...: with -S, relight the frame under one weight 0..255 per light of -L / -M]\n"
+              "       [-K samples[,radius]: with -S, the relit frame times that many samples of ambient occlusion]\n"
               "       env RT_KERNEL_DIR: kernel images; RT_ASSETS_PATHS: search directories\n");
 }
 #endif
@@ -164,6 +172,7 @@ int main(int argc, char** argv) {
     case 'V': aov_file = optarg; break;
     case 'W': weights_arg = optarg; break;
     case 'D': denoise_arg = optarg; break;
+    case 'K': ao_arg = optarg; break;
 #endif
     case '?': usage(); return 0;
     default: usage(); return -1;  // -i: in the reference's option string, never handled
@@ -224,6 +233,16 @@ int main(int argc, char** argv) {
     if (!ok || weights.size() != more_lights.size() + 1) {
       std::printf("Error: -W w0,w1,... needs -S, one rank and one weight in 0..255 per light of -L / -M (%zu)\n",
                   more_lights.size() + 1);
+      usage();
+      return 1;
+    }
+  }
+  uint32_t ao_samples = 0;
+  rt_ao_params_t ao{__builtin_inff(), RT_AO_DEFAULT_SEED};
+  if (ao_arg) {
+    const int got = std::sscanf(ao_arg, "%u,%f", &ao_samples, &ao.radius);
+    if (!shadows || rank >= 0 || got < 1 || ao_samples < 1 || ao_samples > 65535u || !(ao.radius > 0.0f)) {
+      std::printf("Error: -K samples[,radius] needs -S, one rank, 1..65535 samples and a positive radius\n");
       usage();
       return 1;
     }
@@ -416,6 +435,21 @@ int main(int argc, char** argv) {
     std::string ws;
     for (size_t i = 0; i < weights.size(); ++i) ws += (i ? "," : "") + std::to_string(weights[i]);
     std::printf("Relight: %zu lights, weights %s\n", weights.size(), ws.c_str());
+  }
+  if (ao_arg) {
+    // the relit frame times its ambient term: the framebuffer written below
+    if (!weights_arg) {
+      weights.assign(more_lights.size() + 1, 1);
+      RT_CHECK(rt_relight_capture(r));
+    }
+    RT_CHECK(rt_renderer_ao_begin(r, &ao));
+    for (uint32_t left = ao_samples; left;) {
+      const uint32_t k = left < 64u ? left : 64u;
+      RT_CHECK(rt_render_ao_start(r, k));
+      left -= k;
+    }
+    RT_CHECK(rt_render_ao_resolve(r, RT_AO_MODULATE, weights.data(), (uint32_t)weights.size()));
+    std::printf("AO: %u samples, radius %g\n", ao_samples, (double)ao.radius);
   }
   int errors = 0;
   if (std::strcmp(output_file, "null") != 0 && (!sharded || rank == 0)) {

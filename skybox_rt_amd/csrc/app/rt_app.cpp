@@ -1409,6 +1409,11 @@ int rt_renderer_configure(rt_renderer_h r, const rt_render_params_t* p) {
   if (release_idle(r, &r->dn_buf) != 0) return -1;
   r->dn_bytes = 0;
   r->dn_captured = false;
+  // and the ambient-occlusion counts; the session is over, and so are the records it read
+  if (release_idle(r, &r->ao_buf) != 0) return -1;
+  r->ao_bytes = 0;
+  r->ao_on = r->ao_reset = r->aov_launched = false;
+  r->ao_n = 0;
   r->nlights = 0;  // a configure returns to one light (rt_renderer_set_lights)
   rt_kernel_arg_t& a = r->arg;
   a.width = p->width;
@@ -1649,8 +1654,9 @@ int rt_renderer_configure(rt_renderer_h r, const rt_render_params_t* p) {
   // (and the visibility records' area: rt_render_aov_start writes it)
   // (and the relight area: rt_relight_capture_start writes it)
   // (and the denoiser's area: rt_denoise_capture_start writes it)
+  // (and the ambient-occlusion area: rt_renderer_ao_begin writes it)
   if (!r->args &&
-      upload(r->dev, nullptr, RT_DENOISE_ARG_OFFSET + sizeof(rt_denoise_arg_t), &r->args, &args_addr))
+      upload(r->dev, nullptr, RT_AO_ARG_OFFSET + sizeof(rt_ao_arg_t), &r->args, &args_addr))
     return -1;
   if (rtapp::write_args(r, 0, &a, sizeof(a)) != 0)
     return fail("render argument upload failed");
@@ -1963,6 +1969,7 @@ static int aov_launch(rt_renderer_h r, vx_buffer_h img) {
   // an ordinary launch (no lane asked for) on the image's own grid: the driver orders it behind
   // the frames in flight on both lanes and ahead of what starts after it
   if (vx_start(r->dev, img, r->args) != 0) return fail("vx_start failed");
+  r->aov_launched = true;
   return 0;
 }
 
@@ -2089,6 +2096,145 @@ uint32_t rt_relight_resolve(uint32_t base_argb, uint32_t depth_flags, uint32_t l
   if (W == 0) return base_argb;
   const rt_relight_div_t d = rt_relight_div(W);
   return rt_relight_mix(base_argb, rt_relight_occluded(light_mask, w, n), W, d.s, d.m);
+}
+
+// ---- ambient occlusion from the visibility records (vx_rt.h; NO REFERENCE) --
+
+int rt_renderer_ao_begin(rt_renderer_h r, const rt_ao_params_t* p) {
+  if (!r || !r->configured) return fail("renderer not configured");
+  if (!p) return fail("null argument");
+  if (const int e = aov_admit(r, "rt_renderer_ao_begin")) return e;
+  if ((r->params.flags & RT_RENDER_COMPACT) || r->params.shard_count > 1)
+    return fail("rt_renderer_ao_begin: a linear framebuffer only (the rays are keyed by y * W + x; compact and "
+                "sharded buffers are in task order)", -2);
+  if (!r->aov || !r->aov_launched)
+    return fail("rt_renderer_ao_begin: no visibility records since the last configure (rt_render_aov, "
+                "rt_relight_capture)", -2);
+  if (!(p->radius > 0.0f))
+    return fail("rt_renderer_ao_begin: the radius must be positive (or +inf), not NaN", -2);
+  if (!r->set_tag || !r->set_words)
+    return fail("rt_renderer_ao_begin: the driver passes no launch tag / words (the launches' parameters)", -2);
+  if (aov_image(r, "rt_ao.vxbin", &r->ao_img) != 0 || aov_image(r, "rt_ao_resolve.vxbin", &r->ao_resolve_img) != 0)
+    return -1;
+  if (!r->ao_buf || r->ao_bytes != r->cbuf_bytes) {
+    // (upload frees the old buffer: not under launches still writing it)
+    if (r->ao_buf && vx_ready_wait(r->dev, VX_MAX_TIMEOUT) != 0) return fail("vx_ready_wait failed");
+    rt_ao_arg_t aa{};
+    r->ao_on = false;
+    r->ao_bytes = 0;
+    if (upload(r->dev, nullptr, r->cbuf_bytes, &r->ao_buf, &aa.ao_addr)) return -1;
+    r->ao_bytes = r->cbuf_bytes;
+    aa.npix = (uint32_t)(r->cbuf_bytes / 4);
+    aa.cbuf1_off = r->cbuf1_off;
+    // behind the launches in flight, ahead of every launch started after it
+    if (rtapp::write_args(r, RT_AO_ARG_OFFSET, &aa, sizeof(aa)) != 0)
+      return fail("ambient occlusion argument upload failed");
+  }
+  r->ao_params = *p;
+  r->ao_on = true;
+  r->ao_reset = true;  // the counts are not cleared: the first launch does not read them
+  r->ao_n = 0;
+  return 0;
+}
+
+int rt_renderer_ao_reset(rt_renderer_h r) {
+  if (!r || !r->configured) return fail("renderer not configured");
+  if (!r->ao_on) return fail("rt_renderer_ao_reset: no session begun (rt_renderer_ao_begin)", -2);
+  r->ao_reset = true;
+  r->ao_n = 0;
+  return 0;
+}
+
+int rt_render_ao_start(rt_renderer_h r, uint32_t samples) {
+  if (!r || !r->configured) return fail("renderer not configured");
+  if (!r->ao_on) return fail("rt_render_ao: no session begun (rt_renderer_ao_begin)", -2);
+  if (samples < 1 || samples > RT_AO_MAX_S) return fail("rt_render_ao: samples must be in [1, 64]", -2);
+  if (r->ao_n + samples > RT_AO_MAX_SAMPLES)
+    return fail("rt_render_ao: more than 65535 samples per pixel (the resolve's 32-bit numerator)", -2);
+  uint32_t lw[4] = {0, 0, 0, 0};
+  std::memcpy(&lw[0], &r->ao_params.radius, 4);
+  lw[1] = r->ao_params.seed + r->ao_n;
+  lw[2] = (samples - 1u) | (r->ao_reset ? RT_AO_LW_RESET : 0u);
+  if (r->set_counters && r->set_counters(r->dev, (r->params.flags & RT_RENDER_COUNTERS) ? 1 : 0) != 0)
+    return fail("vx_hip_set_counters failed");
+  if (r->set_words(r->dev, lw, 4) != 0) return fail("vx_hip_set_launch_words failed");
+  if (r->set_tag(r->dev, 0) != 0) return fail("vx_hip_set_launch_tag failed");
+  // an ordinary launch (no lane asked for) on the image's own grid, as a record launch goes
+  if (vx_start(r->dev, r->ao_img, r->args) != 0) return fail("vx_start failed");
+  r->ao_n += samples;
+  r->ao_reset = false;
+  return 0;
+}
+
+int rt_render_ao(rt_renderer_h r, uint32_t samples) {
+  const int e = rt_render_ao_start(r, samples);
+  return e ? e : rt_render_wait(r);
+}
+
+int rt_renderer_ao_samples(rt_renderer_h r, uint32_t* n) {
+  if (!r || !n) return fail("null argument");
+  if (!r->configured || !r->ao_on) return fail("rt_renderer_ao_samples: no session begun (rt_renderer_ao_begin)", -2);
+  *n = r->ao_n;
+  return 0;
+}
+
+int rt_read_ao(rt_renderer_h r, uint32_t* out, uint64_t count) {
+  if (!r || !out || !r->configured) return fail("renderer not configured");
+  if (!r->ao_on) return fail("rt_read_ao: no session begun (rt_renderer_ao_begin)", -2);
+  if (r->ao_n == 0) return fail("rt_read_ao: no sample traced since the last begin / reset (rt_render_ao)", -2);
+  if (count * 4 < r->ao_bytes) return fail("buffer too small");
+  return vx_copy_from_dev(out, r->ao_buf, 0, r->ao_bytes) == 0 ? 0 : fail("vx_copy_from_dev failed");
+}
+
+int rt_render_ao_resolve_start(rt_renderer_h r, uint32_t mode, const uint8_t* weights, uint32_t n) {
+  if (!r || !r->configured) return fail("renderer not configured");
+  if (!r->ao_on) return fail("rt_render_ao_resolve: no session begun (rt_renderer_ao_begin)", -2);
+  if (r->ao_n == 0) return fail("rt_render_ao_resolve: no sample traced since the last begin / reset (N = 0)", -2);
+  if (mode != RT_AO_GREY && mode != RT_AO_MODULATE) return fail("rt_render_ao_resolve: unknown mode", -2);
+  uint32_t lw[4] = {0, 0, 0, 0}, tag = r->ao_n << RT_AO_TAG_SAMPLES_SHIFT;
+  if (mode == RT_AO_MODULATE) {
+    if (r->relight_n == 0)
+      return fail("rt_render_ao_resolve: RT_AO_MODULATE without a relight capture since the last configure / "
+                  "set_light / set_lights (rt_relight_capture)", -2);
+    tag |= RT_AO_TAG_MODULATE;
+    if (weights) {
+      if (n != r->relight_n)
+        return fail("rt_render_ao_resolve: " + std::to_string(n) + " weights for the capture's " +
+                    std::to_string(r->relight_n) + " lights", -2);
+      uint32_t W = 0;
+      std::memcpy(lw, weights, n);
+      for (uint32_t i = 0; i < n; ++i) W += weights[i];
+      if (W == 0) return fail("rt_render_ao_resolve: every weight is 0", -2);
+      tag |= RT_AO_TAG_WEIGHTS | n;
+    }
+  }
+  // into the framebuffer in use, as a relight launch goes: no flip, no lane
+  const int buf = r->cur_buf < 0 ? 0 : r->cur_buf;
+  tag |= buf ? RT_AO_TAG_CBUF1 : 0u;
+  // (the launch counts nothing: no counter rows)
+  if (r->set_counters && r->set_counters(r->dev, 0) != 0) return fail("vx_hip_set_counters failed");
+  if (r->set_words(r->dev, lw, 4) != 0) return fail("vx_hip_set_launch_words failed");
+  if (r->set_tag(r->dev, tag) != 0) return fail("vx_hip_set_launch_tag failed");
+  if (vx_start(r->dev, r->ao_resolve_img, r->args) != 0) return fail("vx_start failed");
+  r->prev_buf = -1;
+  r->cur_buf = buf;
+  return 0;
+}
+
+int rt_render_ao_resolve(rt_renderer_h r, uint32_t mode, const uint8_t* weights, uint32_t n) {
+  const int e = rt_render_ao_resolve_start(r, mode, weights, n);
+  return e ? e : rt_render_wait(r);
+}
+
+uint32_t rt_ao_resolve(uint32_t argb, uint32_t occluded, uint32_t n) {
+  if (n == 0) return argb;
+  const uint64_t N = n, o = occluded < n ? occluded : n;
+  uint32_t out = argb & 0xff000000u;
+  for (int sh = 0; sh <= 16; sh += 8) {
+    const uint64_t c = (argb >> sh) & 0xffu;
+    out |= (uint32_t)((2 * c * (N - o) + N) / (2 * N)) << sh;
+  }
+  return out;
 }
 
 // ---- denoising accumulated path frames (vx_rt.h; NO REFERENCE) -------------

@@ -139,6 +139,16 @@ struct rt_renderer {
   vx_buffer_h dn_guide_img = nullptr, dn_prep_img = nullptr, dn_pass_img = nullptr, dn_buf = nullptr;
   uint64_t dn_bytes = 0;
   bool dn_captured = false;
+  // ambient occlusion (vx_rt.h rt_renderer_ao_begin / rt_render_ao_start / rt_render_ao_resolve_start):
+  // the rt_ao and rt_ao_resolve images, loaded and kept the same way, and the count buffer of the
+  // current configuration (rt_common.h rt_ao_arg_t: 4 B per framebuffer pixel)
+  vx_buffer_h ao_img = nullptr, ao_resolve_img = nullptr, ao_buf = nullptr;
+  uint64_t ao_bytes = 0;
+  bool aov_launched = false;  // a record launch was queued since the last configure
+  bool ao_on = false;         // between ao_begin and the next configure
+  bool ao_reset = false;      // the next tracing launch carries RT_AO_LW_RESET
+  uint32_t ao_n = 0;          // samples queued since the last reset: the counts' N once they ran
+  rt_ao_params_t ao_params{};
   vx_buffer_h nodes = nullptr, nodes4 = nullptr, tris = nullptr, layers = nullptr, dcs = nullptr, tex = nullptr;
   vx_buffer_h ptris = nullptr, geom = nullptr, oms = nullptr, bbox = nullptr, zbuf = nullptr;
   vx_buffer_h order = nullptr;
@@ -260,7 +270,7 @@ struct rt_renderer {
                            &cbuf, &cbuf1, &args, &verts, &pdc, &dcz, &layer_list, &geometry_list, &vis,
                            &blist, &bidx, &btrim, &btidx, &btrim_img, &btrim_args, &cdesc, &bglayer, &sidx, &slist, &pathq, &pathq_ctr, &oidx, &olist, &ovtris,
                            &accum, &aov, &aov_img, &relight_base, &aov_base_img, &relight_img,
-                           &dn_guide_img, &dn_prep_img, &dn_pass_img, &dn_buf};
+                           &dn_guide_img, &dn_prep_img, &dn_pass_img, &dn_buf, &ao_img, &ao_resolve_img, &ao_buf};
     for (auto* b : bufs) {
       if (*b) vx_mem_free(*b);
       *b = nullptr;

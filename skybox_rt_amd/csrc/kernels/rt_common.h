@@ -465,6 +465,73 @@ static inline uint32_t rt_dn_remod(uint32_t I, uint32_t a) {
   const uint32_t v = (I * a + 128u) >> 8;
   return v > 255u ? 255u : v;
 }
+// Ambient occlusion from the visibility records (vx_rt.h rt_renderer_ao_begin / rt_render_ao_start /
+// rt_render_ao_resolve_start).  The tracing launch (rt_ao_kernel.hip, image rt_ao) reads the record
+// buffer of rt_aov_arg_t and adds, per framebuffer pixel, its occluded samples to one uint32 of the
+// count buffer; the resolve launch (rt_ao_resolve_kernel.hip, image rt_ao_resolve) streams the counts
+// -- and for RT_AO_MODULATE records and base colours -- into the framebuffer in use.  Their argument
+// area, behind the seven above, which stay where they are: written when the buffer is allocated, in
+// stream order, constant until the next configure.  Linear W * H framebuffers only.
+typedef struct {
+  uint64_t ao_addr;     // the count buffer, one uint32 per framebuffer pixel
+  uint32_t npix;        // framebuffer pixels
+  uint32_t cbuf1_off;   // the second framebuffer past arg.cbuf_addr, mod 2^32 (RT_AO_TAG_CBUF1)
+} rt_ao_arg_t;
+#define RT_AO_ARG_OFFSET (RT_DENOISE_ARG_OFFSET + sizeof(rt_denoise_arg_t))
+// A tracing launch's words: w[0] = the radius (float bits; +inf admitted), w[1] = seed + the sample
+// cursor of the launch's first sample (mod 2^32), w[2] = the bits below, w[3] = 0
+#define RT_AO_LW_S_MASK 0x3fu      // bits 0-5: the launch's samples per ray pixel minus one (1..64)
+#define RT_AO_LW_RESET  0x40u      // bit 6: the launch treats every count as zero and does not read it
+#define RT_AO_MAX_S 64u
+#define RT_AO_MAX_SAMPLES 65535u   // the sample cursor's cap: 2 * 255 * N + N fits 32 bits with room
+// A resolve launch's words are RT_AO_MODULATE's 16 weight bytes (as a relight launch's); its tag:
+#define RT_AO_TAG_N_MASK   0x1fu   // bits 0-4: RT_AO_MODULATE under weights: the capture's lights, 1..RT_MAX_LIGHTS
+#define RT_AO_TAG_CBUF1    0x20u   // bit 5: the framebuffer in use is the second one
+#define RT_AO_TAG_MODULATE 0x40u   // bit 6: RT_AO_MODULATE (else RT_AO_GREY)
+#define RT_AO_TAG_WEIGHTS  0x80u   // bit 7: RT_AO_MODULATE relights the base colour under the words' weights
+#define RT_AO_TAG_SAMPLES_SHIFT 8  // bits 8-23: N, the samples in the counts, 1..65535
+// floor(x / d) for 1 <= d < 2^18 and x <= 256 * d, exact, from rd = 1.0f / (float)d (IEEE binary32, wave-
+// uniform in the kernel: d depends on the launch alone).  (float)x is within 2^-24 of x relatively, rd
+// within 2^-24 of 1 / d, their product rounds once more: the estimate is within 4 * 2^-24 * 256 = 2^-14
+// of x / d, so its floor is floor(x / d) or one to either side, and one multiply-subtract tells which:
+// the remainder against 0 and d.  q * d <= 257 * 2^18 fits 32 bits.
+#if defined(__HIPCC__)
+__host__ __device__
+#endif
+static inline uint32_t rt_ao_quot(uint32_t x, uint32_t d, float rd) {
+  uint32_t q = (uint32_t)((float)x * rd);
+  const int32_t r = (int32_t)(x - q * d);
+  q = r < 0 ? q - 1u : q;
+  q = r >= (int32_t)d ? q + 1u : q;
+  return q;
+}
+// The ambient term on a pixel (vx_rt.h rt_ao_resolve): per colour channel c of argb, (2 * c * (N - o) +
+// N) / (2 * N) in integer division -- c scaled by the unoccluded share, rounded half up -- under argb's
+// alpha byte; N = 1..65535 samples, o <= N of them occluded.  rd = 1.0f / (float)(2 * N).
+#if defined(__HIPCC__)
+__host__ __device__
+#endif
+static inline uint32_t rt_ao_mix(uint32_t argb, uint32_t o, uint32_t N, float rd) {
+  uint32_t out = argb & 0xff000000u;
+  for (int sh = 0; sh <= 16; sh += 8) {
+    const uint32_t c = (argb >> sh) & 0xffu;
+    out |= rt_ao_quot(2u * c * (N - o) + N, 2u * N, rd) << sh;
+  }
+  return out;
+}
+// rt_relight_mix's pixel through rt_ao_quot (d = 2 * W <= 8160, x <= 255.5 * d): the same quotients,
+// without the multiplier the relight launch's tag carries (the resolve launch's tag holds N instead)
+#if defined(__HIPCC__)
+__host__ __device__
+#endif
+static inline uint32_t rt_ao_relight_mix(uint32_t base, uint32_t O, uint32_t W, float rd) {
+  uint32_t out = base & 0xff000000u;
+  for (int sh = 0; sh <= 16; sh += 8) {
+    const uint32_t c = (base >> sh) & 0xffu;
+    out |= rt_ao_quot(2u * ((W - O) * c + O * (c >> 1)) + W, 2u * W, rd) << sh;
+  }
+  return out;
+}
 // A path-traced frame lit by several point lights (pt_kernel.hip PT_LIGHTS, images pt_lights /
 // pt_lights_accum; vx_rt.h rt_renderer_set_path_lights) reads the first count <=
 // RT_MAX_PATH_LIGHTS entries of the same table, every one with lists (slist_on 1).  The cap is

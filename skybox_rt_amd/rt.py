@@ -94,6 +94,13 @@ DENOISE_PASSES, DENOISE_DEPTH_SHIFT, DENOISE_COLOR_SHIFT = 2, 2, 3   # vx_rt.h R
 RT_AOV_DEPTH_MASK = 0xFFFFFF
 RT_AOV_GEOM = 0x01000000
 RT_AOV_SHADOW_RAY = 0x02000000
+# ambient occlusion (vx_rt.h rt_ao_params_t, RT_AO_GREY / RT_AO_MODULATE)
+AO_SEED = PT_SEED
+AO_MODES = {"grey": 0, "modulate": 1}
+
+
+class AoParams(C.Structure):
+    _fields_ = [("radius", C.c_float), ("seed", C.c_uint32)]
 
 
 class RenderParams(C.Structure):
@@ -197,6 +204,14 @@ def lib():
             "rt_render_denoise": [vp, vp],
             "rt_read_denoise_guide": [vp, vp, vp, u64],
             "rt_write_accum": [vp, vp, u64, u32],
+            "rt_renderer_ao_begin": [vp, C.POINTER(AoParams)],
+            "rt_renderer_ao_reset": [vp],
+            "rt_render_ao_start": [vp, u32],
+            "rt_render_ao": [vp, u32],
+            "rt_renderer_ao_samples": [vp, C.POINTER(u32)],
+            "rt_read_ao": [vp, vp, u64],
+            "rt_render_ao_resolve_start": [vp, u32, vp, u32],
+            "rt_render_ao_resolve": [vp, u32, vp, u32],
         }
         for name, argtypes in sig.items():
             fn = getattr(h, name)
@@ -212,6 +227,8 @@ def lib():
         h.rt_aov_relight.restype = u32
         h.rt_relight_resolve.argtypes = [u32, u32, u32, vp, u32]
         h.rt_relight_resolve.restype = u32
+        h.rt_ao_resolve.argtypes = [u32, u32, u32]
+        h.rt_ao_resolve.restype = u32
         h.rt_last_error.restype = C.c_char_p
         h.rt_last_error.argtypes = []
         _h = h
@@ -689,6 +706,60 @@ class Renderer:
         _check(lib().rt_read_relight_base(self._h, out.ctypes.data, out.size), "rt_read_relight_base")
         return out
 
+    # ambient occlusion from the records (vx_rt.h rt_renderer_ao_begin; images rt_ao, rt_ao_resolve)
+    def ao_begin(self, radius: float = float("inf"), seed: int = AO_SEED) -> None:
+        """Begin an ambient-occlusion session on the visibility records of the last
+        aov() / relight_capture(): rays of at most `radius` (positive, or inf),
+        sample c keyed by seed + c.  Linear framebuffers only.  set_light() and
+        set_lights() do not end it; configure() does."""
+        p = AoParams(float(radius), int(seed) & 0xFFFFFFFF)
+        _check(lib().rt_renderer_ao_begin(self._h, C.byref(p)), "rt_renderer_ao_begin")
+
+    def ao_reset(self) -> None:
+        """The sample cursor back to 0; the next ao() launch overwrites the counts."""
+        _check(lib().rt_renderer_ao_reset(self._h), "rt_renderer_ao_reset")
+
+    def ao(self, samples: int, wait: bool = True) -> None:
+        """One launch tracing `samples` (1..64) more any-hit rays per ray pixel --
+        cosine-weighted about the pixel's geometric normal, the path tracer's first
+        bounce -- and adding the occluded ones to the pixel's count (ao_records()).
+        It writes neither the framebuffer nor the visibility records."""
+        fn = lib().rt_render_ao if wait else lib().rt_render_ao_start
+        _check(fn(self._h, int(samples)), "rt_render_ao" if wait else "rt_render_ao_start")
+
+    def ao_samples(self) -> int:
+        """N: the samples traced per ray pixel since ao_begin() / ao_reset()."""
+        n = C.c_uint32()
+        _check(lib().rt_renderer_ao_samples(self._h, C.byref(n)), "rt_renderer_ao_samples")
+        return int(n.value)
+
+    def ao_records(self) -> np.ndarray:
+        """The occluded samples per pixel, uint32 [H, W] (waits for the device)."""
+        p = self.params
+        if p is None:
+            raise RtError("rt_read_ao failed: renderer not configured")
+        out = np.zeros((p.height, p.width), np.uint32)
+        _check(lib().rt_read_ao(self._h, out.ctypes.data, out.size), "rt_read_ao")
+        return out
+
+    def ao_resolve(self, mode: str = "grey", weights=None, wait: bool = True) -> None:
+        """One streaming launch writing the ambient term into the framebuffer in
+        use: mode "grey" the term on white, rt.ao_resolve(0xffffffff, o, N);
+        "modulate" the term on the relit pixel of the live relight_capture() under
+        `weights` (as relight() takes them), or on the base colour itself with
+        weights=None."""
+        if mode not in AO_MODES:
+            raise RtError(f"rt_render_ao_resolve failed: mode is one of {sorted(AO_MODES)}")
+        wp, n = None, 0
+        if weights is not None:
+            w = np.asarray(weights)
+            if w.ndim != 1 or w.size == 0 or (w < 0).any() or (w > 255).any():
+                raise RtError("rt_render_ao_resolve failed: weights are 0..255, one per light")
+            w = np.ascontiguousarray(w, np.uint8)
+            wp, n = w.ctypes.data, w.size
+        fn = lib().rt_render_ao_resolve if wait else lib().rt_render_ao_resolve_start
+        _check(fn(self._h, AO_MODES[mode], wp, n), "rt_render_ao_resolve" if wait else "rt_render_ao_resolve_start")
+
     # denoising accumulated path frames (vx_rt.h rt_denoise_capture_start; images rt_aov_guide,
     # rt_denoise_prep, rt_denoise_pass)
     def denoise_capture(self, wait: bool = True) -> None:
@@ -891,6 +962,21 @@ def relight_resolve(base_argb, depth_flags, light_mask, weights):
     uniq, inv = np.unique(key.reshape(-1), return_inverse=True)
     vals = np.array([fn(int(u >> np.uint64(32)), RT_AOV_SHADOW_RAY if (int(u) >> 16) & 1 else 0, int(u) & 0xFFFF, wp, n)
                      for u in uniq], np.uint32)
+    return vals[inv.reshape(-1)].reshape(a.shape)
+
+
+def ao_resolve(argb, occluded, n: int):
+    """rt_ao_resolve: the ambient term on a pixel -- per colour channel c of argb
+    (2 * c * (n - occluded) + n) // (2 * n) under argb's alpha byte; argb when n is
+    0.  Scalars give an int; arrays (broadcast against each other) a uint32 array,
+    the library's function applied to every distinct (pixel, count) pair."""
+    fn = lib().rt_ao_resolve
+    if np.ndim(argb) == 0 and np.ndim(occluded) == 0:
+        return int(fn(int(argb) & 0xFFFFFFFF, int(occluded) & 0xFFFFFFFF, int(n)))
+    a, o = np.broadcast_arrays(np.asarray(argb).astype(np.uint32), np.asarray(occluded).astype(np.uint32))
+    key = (a.astype(np.uint64) << np.uint64(32)) | o.astype(np.uint64)
+    uniq, inv = np.unique(key.reshape(-1), return_inverse=True)
+    vals = np.array([fn(int(u >> np.uint64(32)), int(u & np.uint64(0xFFFFFFFF)), int(n)) for u in uniq], np.uint32)
     return vals[inv.reshape(-1)].reshape(a.shape)
 
 
