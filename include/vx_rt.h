@@ -786,6 +786,115 @@ int rt_render_ao_resolve(rt_renderer_h r, uint32_t mode, const uint8_t* weights,
 /* the resolved pixel restated on the host (occluded above n counts as n) */
 uint32_t rt_ao_resolve(uint32_t argb, uint32_t occluded, uint32_t n);
 
+/* Caller-supplied rays against the scene's tree: closest-hit and any-hit
+ * queries, batched, on the device.  NO REFERENCE (the walks are rt_trace.h's
+ * trace<false> / trace<true>, which tests/test_gpu_ray_kat.py holds to the exact
+ * model; tests/test_gpu_query.py holds this entry point to the same answers).
+ *
+ * Space.  Rays are in the space the scene is traced in: clip (x, y, w), the eye
+ * at the origin -- rt_renderer_set_light's space, and the space of the
+ * triangles' corners.  pid is the scene's primitive index, the visibility
+ * records' pid.  Only geometry primitives (depth-tested drawcalls: the tree's
+ * triangles) can be hit.
+ *
+ * RT_QUERY_CLOSEST.  Of the triangles k != skip that Moeller-Trumbore (mt_hit,
+ * inclusive coverage on the edges) meets at tmin < t < tmax, both strict -- the
+ * limits as trace<false> applies them: mt_hit's t > tmin, and a best hit that
+ * starts at tmax and is replaced by t < best -- the one with the smallest t; at
+ * equal t the lowest pid (tie_high = false).  t is mt_hit's value, bit for bit.
+ * RT_QUERY_ANY.  A miss iff no such triangle exists; else
+ * the pid and t of the occluder the fixed-order any-hit walk (trace<true>)
+ * finds first: deterministic for a given tree, but not the closest -- the
+ * caller may rely on pid >= 0 only.
+ * A miss is {-1, 0.0f}.
+ * Malformed rays.  A ray is a miss, and walks nothing, when its direction is
+ * all zero (+-0), when any of its 8 words is NaN, or when its origin or its
+ * direction has an infinite component.  tmax = +inf is admitted.  The other
+ * lanes of its wave are not affected.
+ * skip.  One int32 per ray, -1 for none: the primitive the ray does not meet
+ * (the frames' own secondary rays avoid their origin's triangle this way).
+ * Without RT_QUERY_SKIP the buffer is not read and no ray skips.
+ * RT_QUERY_PERM.  Slot q of the launch traces ray perm[q] and stores its hit
+ * at hits[perm[q]]: results stay at the rays' own indices, only the assignment
+ * of rays to waves changes (a wave takes 64 consecutive slots).  perm must be a
+ * permutation of [0, n); a slot whose entry is >= n traces and stores nothing.
+ *
+ * The coherence key of a ray, a uint32 (rt_query_key; every operation is one
+ * binary32 operation, in the order written, none fused):
+ *   malformed ray: 0xFFFFFFFF.
+ *   bits 31, 30, 29: the sign bits of d.x, d.y, d.z (the words' bit 31).
+ *   bits 28..8: the 21-bit Morton code of the origin's cell, 128 cells per axis
+ *     over box = {lo.x, lo.y, lo.z, hi.x, hi.y, hi.z}, axis a's 7 bits c_a at
+ *     key bits 8 + a + 3 i (x lowest):
+ *       inv_a = hi_a > lo_a ? 128.0f / (hi_a - lo_a) : 0.0f   (once, on the host)
+ *       c_a = (uint32_t)fminf(fmaxf((o_a - lo_a) * inv_a, 0.0f), 127.0f)
+ *     (fmaxf of a NaN and 0 is 0: an overflowing difference on a flat axis).
+ *   bits 7..4 / 3..0: the direction's cell, with s = (|d.x| + |d.y|) + |d.z|:
+ *       (uint32_t)fminf((|d.y| / s) * 16.0f, 15.0f)  /  the same of |d.x|.
+ * The launches' box is the bounding box of the geometry triangles' corners
+ * (rt_query_buffers_t::box; all zero for a scene without geometry), which the
+ * tree's root box encloses.
+ *
+ * rt_query_reserve(r, max_rays): one arena allocation of 52 B per ray -- rays,
+ * hits, skip words, permutation, keys -- for max_rays = 1 .. 2^24 rays, and its
+ * addresses into the argument block in stream order.  The renderer must be
+ * configured (the kernels read the scene through its argument block); the
+ * reserve then survives rt_renderer_configure, rt_renderer_set_light and
+ * rt_renderer_set_lights, until the next reserve or rt_renderer_free.  -2 when
+ * the arena cannot hold the buffers (the old reserve is kept), when max_rays
+ * is out of range, or when launches using a previous reserve were started and
+ * not waited for (rt_render_wait).  Loads rt_query.vxbin and
+ * rt_query_keys.vxbin (the kernel directory's, else the library's) on the
+ * first call.  The buffers' contents are undefined until written.
+ * rt_query_buffers: the true device pointers, as rt_framebuffer_device gives
+ * the framebuffer's, for code on the renderer's stream (rt_device_stream):
+ * ordinary launches -- the query launches among them -- run on that stream.
+ * rt_query_write_*: host uploads in stream order behind the queued launches
+ * (copies above the driver's staging slot wait for the device first); first +
+ * n <= the capacity.
+ * rt_query_trace_start(r, n, mode, flags): one launch of rt_query (kernels/
+ * rt_query_kernel.hip) over rays [0, n) -- under RT_QUERY_PERM over slots [0, n)
+ * -- with no host wait and no copy; rt_render_wait covers it.  It writes
+ * hits [0, n) only: no framebuffer, no record buffer, no counter.  Any frame
+ * kind may be configured as long as the tree is the binary16 BVH4 (a scene
+ * without geometry: every ray a miss).  -2: not configured, no reserve, n = 0
+ * or above the capacity, an unknown mode or flag, a tree of another layout, a
+ * driver without launch words.
+ * rt_query_keys_start(r, n): one launch of rt_query_keys (kernels/
+ * rt_query_keys_kernel.hip) writing keys [0, n): 32 B in, 4 B out per ray,
+ * nothing traced.  Sorting is the caller's: a stable sort of the keys gives the
+ * permutation for RT_QUERY_PERM.
+ * rt_query_read_*: wait for the device, then copy out. */
+typedef struct { float o[3], tmin, d[3], tmax; } rt_ray_t;   /* 32 B */
+typedef struct { int32_t pid; float t; } rt_hit_t;           /* 8 B; a miss is {-1, 0.0f} */
+#define RT_QUERY_CLOSEST 0u
+#define RT_QUERY_ANY 1u
+#define RT_QUERY_SKIP 0x1u   /* flags: read the skip buffer */
+#define RT_QUERY_PERM 0x2u   /* flags: slot q traces ray perm[q] */
+#define RT_QUERY_MAX_RAYS (1u << 24)
+typedef struct {
+  void*    rays;      /* rt_ray_t [capacity] */
+  void*    hits;      /* rt_hit_t [capacity] */
+  void*    skip;      /* int32_t  [capacity] */
+  void*    perm;      /* uint32_t [capacity] */
+  void*    keys;      /* uint32_t [capacity] */
+  uint64_t capacity;  /* rays */
+  float    box[6];    /* the key grid's box: lo.xyz, hi.xyz */
+} rt_query_buffers_t;
+int rt_query_reserve(rt_renderer_h r, uint64_t max_rays);
+int rt_query_buffers(rt_renderer_h r, rt_query_buffers_t* out);
+int rt_query_write_rays(rt_renderer_h r, const rt_ray_t* rays, uint64_t first, uint64_t n);
+int rt_query_write_skip(rt_renderer_h r, const int32_t* skip, uint64_t first, uint64_t n);
+int rt_query_write_perm(rt_renderer_h r, const uint32_t* perm, uint64_t first, uint64_t n);
+int rt_query_trace_start(rt_renderer_h r, uint64_t n, uint32_t mode, uint32_t flags);
+int rt_query_trace(rt_renderer_h r, uint64_t n, uint32_t mode, uint32_t flags);   /* start + wait */
+int rt_query_keys_start(rt_renderer_h r, uint64_t n);
+int rt_query_keys(rt_renderer_h r, uint64_t n);                                   /* start + wait */
+int rt_query_read_hits(rt_renderer_h r, rt_hit_t* out, uint64_t first, uint64_t n);
+int rt_query_read_keys(rt_renderer_h r, uint32_t* out, uint64_t first, uint64_t n);
+/* a ray's key restated on the host */
+uint32_t rt_query_key(const rt_ray_t* ray, const float box[6]);
+
 /* Read back one per-resolution record array of the current configuration
  * (layouts: kernels/rt_common.h; NO REFERENCE).  out NULL = size query
  * (*size = bytes). */

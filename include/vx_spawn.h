@@ -156,6 +156,11 @@ struct vx_arena {
   __device__ __forceinline__ void st_u32(uint32_t off, uint32_t v) const {
     __builtin_amdgcn_raw_buffer_store_b32(v, r, off, 0, 0);
   }
+  __device__ __forceinline__ void st_u2(uint32_t off, uint2 v) const {
+    typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+    const u32x2 w = {v.x, v.y};
+    __builtin_amdgcn_raw_buffer_store_b64(w, r, off, 0, 0);
+  }
   __device__ __forceinline__ void st_u4(uint32_t off, uint4 v) const {
     typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
     const u32x4 w = {v.x, v.y, v.z, v.w};

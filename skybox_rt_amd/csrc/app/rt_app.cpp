@@ -1655,8 +1655,9 @@ int rt_renderer_configure(rt_renderer_h r, const rt_render_params_t* p) {
   // (and the relight area: rt_relight_capture_start writes it)
   // (and the denoiser's area: rt_denoise_capture_start writes it)
   // (and the ambient-occlusion area: rt_renderer_ao_begin writes it)
+  // (and the ray queries' area: rt_query_reserve writes it)
   if (!r->args &&
-      upload(r->dev, nullptr, RT_AO_ARG_OFFSET + sizeof(rt_ao_arg_t), &r->args, &args_addr))
+      upload(r->dev, nullptr, RT_QUERY_ARG_OFFSET + sizeof(rt_query_arg_t), &r->args, &args_addr))
     return -1;
   if (rtapp::write_args(r, 0, &a, sizeof(a)) != 0)
     return fail("render argument upload failed");
@@ -1806,7 +1807,9 @@ int render_start(rt_renderer_h r, bool sync, uint32_t accum_k) {
 
 int rt_render_wait(rt_renderer_h r) {
   if (!r) return fail("null argument");
-  return vx_ready_wait(r->dev, VX_MAX_TIMEOUT) == 0 ? 0 : fail("vx_ready_wait failed");
+  if (vx_ready_wait(r->dev, VX_MAX_TIMEOUT) != 0) return fail("vx_ready_wait failed");
+  r->q_pending = false;  // (the query launches have run: rt_query_reserve may replace their buffers)
+  return 0;
 }
 
 int rt_render(rt_renderer_h r) {
@@ -2235,6 +2238,216 @@ uint32_t rt_ao_resolve(uint32_t argb, uint32_t occluded, uint32_t n) {
     out |= (uint32_t)((2 * c * (N - o) + N) / (2 * N)) << sh;
   }
   return out;
+}
+
+// ---- caller-supplied rays: closest-hit and any-hit queries (vx_rt.h; NO REFERENCE) ----
+
+static_assert(sizeof(rt_ray_t) == 32 && sizeof(rt_hit_t) == 8, "the query records: 32-B rays, 8-B hits");
+
+namespace {
+
+// the reserve's one buffer: rays | hits | skip | perm | keys, each 16-B aligned (the capacity is kept a
+// multiple of 4 rays)
+struct QueryLayout {
+  uint64_t rays, hits, skip, perm, keys, bytes;
+};
+QueryLayout query_layout(uint64_t cap) {
+  QueryLayout l;
+  l.rays = 0;
+  l.hits = l.rays + 32 * cap;
+  l.skip = l.hits + 8 * cap;
+  l.perm = l.skip + 4 * cap;
+  l.keys = l.perm + 4 * cap;
+  l.bytes = l.keys + 4 * cap;
+  return l;
+}
+
+// the key grid's box: the bounds of the geometry triangles' clip (x, y, w) corners; zeros without geometry
+void query_box(const rt_scene* s, float box[6]) {
+  for (int k = 0; k < 6; ++k) box[k] = 0.0f;
+  bool first = true;
+  for (const uint32_t g : s->geometry) {
+    const auto& p = s->scene.prims[g];
+    for (int c = 0; c < 3; ++c) {
+      const float v[3] = {p[c].pos[0], p[c].pos[1], p[c].pos[3]};
+      for (int k = 0; k < 3; ++k) {
+        if (first || v[k] < box[k]) box[k] = v[k];
+        if (first || v[k] > box[3 + k]) box[3 + k] = v[k];
+      }
+      first = false;
+    }
+  }
+}
+
+void query_grid(const float box[6], float lo[3], float inv[3]) {
+  for (int k = 0; k < 3; ++k) {
+    lo[k] = box[k];
+    inv[k] = box[3 + k] > box[k] ? 128.0f / (box[3 + k] - box[k]) : 0.0f;
+  }
+}
+
+int query_ready(rt_renderer_h r, const char* who, uint64_t first, uint64_t n, bool launch) {
+  if (!r || !r->configured) return fail(std::string(who) + ": renderer not configured", -2);
+  if (!r->q_buf || r->q_cap == 0) return fail(std::string(who) + ": no reserve (rt_query_reserve)", -2);
+  if (n == 0) return fail(std::string(who) + ": n is 0", -2);
+  if (first > r->q_cap || n > r->q_cap - first)
+    return fail(std::string(who) + ": " + std::to_string(first) + " + " + std::to_string(n) +
+                " rays is above the reserve's capacity of " + std::to_string(r->q_cap), -2);
+  if (launch) {
+    if (!r->set_words)
+      return fail(std::string(who) + ": the driver passes no launch words (the launch's n, mode and flags)", -2);
+    if (r->arg.num_geom > 0 && !(r->arg.flags & RT_FLAG_BVH4H))
+      return fail(std::string(who) + ": rt_query walks the binary16 BVH4 only; this configuration's tree is "
+                  "another layout", -2);
+  }
+  return 0;
+}
+
+int query_launch(rt_renderer_h r, vx_buffer_h img, uint64_t n, uint32_t w1) {
+  const uint32_t lw[4] = {(uint32_t)n, w1, 0u, 0u};
+  // (the launch counts nothing: no counter rows)
+  if (r->set_counters && r->set_counters(r->dev, 0) != 0) return fail("vx_hip_set_counters failed");
+  if (r->set_words(r->dev, lw, 4) != 0) return fail("vx_hip_set_launch_words failed");
+  if (r->set_tag && r->set_tag(r->dev, 0) != 0) return fail("vx_hip_set_launch_tag failed");
+  // an ordinary launch (no lane asked for) on the image's own grid, as a record launch goes: behind the
+  // frames in flight, ahead of what starts after it
+  if (vx_start(r->dev, img, r->args) != 0) return fail("vx_start failed");
+  r->q_pending = true;
+  return 0;
+}
+
+}  // namespace
+
+int rt_query_reserve(rt_renderer_h r, uint64_t max_rays) {
+  if (!r || !r->configured) return fail("rt_query_reserve: renderer not configured", -2);
+  if (max_rays == 0 || max_rays > RT_QUERY_MAX_RAYS)
+    return fail("rt_query_reserve: max_rays must be in [1, " + std::to_string(RT_QUERY_MAX_RAYS) + "]", -2);
+  if (r->q_buf && r->q_pending)
+    return fail("rt_query_reserve: query launches on the current reserve were started and not waited for "
+                "(rt_render_wait)", -2);
+  if (aov_image(r, "rt_query.vxbin", &r->q_img) != 0 || aov_image(r, "rt_query_keys.vxbin", &r->q_keys_img) != 0)
+    return -1;
+  const uint64_t cap = (max_rays + 3) & ~3ull;
+  const QueryLayout l = query_layout(cap);
+  // the new buffer first: a reserve the arena cannot hold leaves the old one in place
+  vx_buffer_h nb = nullptr;
+  uint64_t addr = 0;
+  if (vx_mem_alloc(r->dev, l.bytes, VX_MEM_READ, &nb) != 0)
+    return fail("rt_query_reserve: the arena cannot hold " + std::to_string(l.bytes) + " bytes for " +
+                std::to_string(max_rays) + " rays", -2);
+  if (vx_mem_address(nb, &addr) != 0 || addr + l.bytes > (1ull << 32)) {
+    vx_mem_free(nb);
+    return fail("rt_query_reserve: the arena cannot hold " + std::to_string(l.bytes) +
+                " bytes below the 4 GiB kernel address range", -2);
+  }
+  if (release_idle(r, &r->q_buf) != 0) {
+    vx_mem_free(nb);
+    return -1;
+  }
+  r->q_buf = nb;
+  r->q_cap = max_rays;
+  query_box(r->sc, r->q_box);
+  rt_query_arg_t qa{};
+  qa.rays_addr = addr + l.rays;
+  qa.hits_addr = addr + l.hits;
+  qa.skip_addr = addr + l.skip;
+  qa.perm_addr = addr + l.perm;
+  qa.keys_addr = addr + l.keys;
+  qa.capacity = (uint32_t)max_rays;
+  query_grid(r->q_box, qa.key_lo, qa.key_inv);
+  // behind the launches in flight (they read the areas in front), ahead of every launch started after it
+  if (rtapp::write_args(r, RT_QUERY_ARG_OFFSET, &qa, sizeof(qa)) != 0) {
+    r->q_cap = 0;
+    return fail("query argument upload failed");
+  }
+  return 0;
+}
+
+int rt_query_buffers(rt_renderer_h r, rt_query_buffers_t* out) {
+  if (!r || !out) return fail("null argument");
+  if (!r->q_buf || r->q_cap == 0) return fail("rt_query_buffers: no reserve (rt_query_reserve)", -2);
+  if (!r->mem_ptr) return fail("rt_query_buffers: the driver gives no device pointers", -2);
+  void* base = nullptr;
+  if (r->mem_ptr(r->q_buf, &base) != 0) return fail("vx_hip_mem_ptr failed");
+  const QueryLayout l = query_layout((r->q_cap + 3) & ~3ull);
+  uint8_t* b = (uint8_t*)base;
+  out->rays = b + l.rays;
+  out->hits = b + l.hits;
+  out->skip = b + l.skip;
+  out->perm = b + l.perm;
+  out->keys = b + l.keys;
+  out->capacity = r->q_cap;
+  std::memcpy(out->box, r->q_box, sizeof(r->q_box));
+  return 0;
+}
+
+static int query_write(rt_renderer_h r, const char* who, const void* src, uint64_t off, uint64_t rec,
+                       uint64_t first, uint64_t n) {
+  if (!src) return fail("null argument");
+  if (const int e = query_ready(r, who, first, n, false)) return e;
+  return rtapp::write_buf(r, r->q_buf, off + rec * first, src, rec * n) == 0
+             ? 0 : fail(std::string(who) + ": upload failed");
+}
+
+int rt_query_write_rays(rt_renderer_h r, const rt_ray_t* rays, uint64_t first, uint64_t n) {
+  return query_write(r, "rt_query_write_rays", rays, r ? query_layout((r->q_cap + 3) & ~3ull).rays : 0, 32, first, n);
+}
+
+int rt_query_write_skip(rt_renderer_h r, const int32_t* skip, uint64_t first, uint64_t n) {
+  return query_write(r, "rt_query_write_skip", skip, r ? query_layout((r->q_cap + 3) & ~3ull).skip : 0, 4, first, n);
+}
+
+int rt_query_write_perm(rt_renderer_h r, const uint32_t* perm, uint64_t first, uint64_t n) {
+  return query_write(r, "rt_query_write_perm", perm, r ? query_layout((r->q_cap + 3) & ~3ull).perm : 0, 4, first, n);
+}
+
+int rt_query_trace_start(rt_renderer_h r, uint64_t n, uint32_t mode, uint32_t flags) {
+  if (const int e = query_ready(r, "rt_query_trace", 0, n, true)) return e;
+  if (mode != RT_QUERY_CLOSEST && mode != RT_QUERY_ANY) return fail("rt_query_trace: unknown mode", -2);
+  if (flags & ~(RT_QUERY_SKIP | RT_QUERY_PERM)) return fail("rt_query_trace: unknown flag", -2);
+  return query_launch(r, r->q_img, n, mode | (flags << RT_QUERY_LW_FLAG_SHIFT));
+}
+
+int rt_query_trace(rt_renderer_h r, uint64_t n, uint32_t mode, uint32_t flags) {
+  const int e = rt_query_trace_start(r, n, mode, flags);
+  return e ? e : rt_render_wait(r);
+}
+
+int rt_query_keys_start(rt_renderer_h r, uint64_t n) {
+  if (const int e = query_ready(r, "rt_query_keys", 0, n, true)) return e;
+  return query_launch(r, r->q_keys_img, n, 0u);
+}
+
+int rt_query_keys(rt_renderer_h r, uint64_t n) {
+  const int e = rt_query_keys_start(r, n);
+  return e ? e : rt_render_wait(r);
+}
+
+static int query_read(rt_renderer_h r, const char* who, void* out, uint64_t off, uint64_t rec, uint64_t first,
+                      uint64_t n) {
+  if (!out) return fail("null argument");
+  if (const int e = query_ready(r, who, first, n, false)) return e;
+  // (the copy waits for the device: the launches before it have run)
+  if (vx_copy_from_dev(out, r->q_buf, off + rec * first, rec * n) != 0) return fail("vx_copy_from_dev failed");
+  r->q_pending = false;
+  return 0;
+}
+
+int rt_query_read_hits(rt_renderer_h r, rt_hit_t* out, uint64_t first, uint64_t n) {
+  return query_read(r, "rt_query_read_hits", out, r ? query_layout((r->q_cap + 3) & ~3ull).hits : 0, 8, first, n);
+}
+
+int rt_query_read_keys(rt_renderer_h r, uint32_t* out, uint64_t first, uint64_t n) {
+  return query_read(r, "rt_query_read_keys", out, r ? query_layout((r->q_cap + 3) & ~3ull).keys : 0, 4, first, n);
+}
+
+uint32_t rt_query_key(const rt_ray_t* ray, const float box[6]) {
+  if (!ray || !box) return RT_QUERY_MISS_KEY;
+  uint32_t w[8];
+  std::memcpy(w, ray, sizeof(w));
+  float lo[3], inv[3];
+  query_grid(box, lo, inv);
+  return rt_query_key_of(w, lo, inv);
 }
 
 // ---- denoising accumulated path frames (vx_rt.h; NO REFERENCE) -------------

@@ -149,6 +149,14 @@ struct rt_renderer {
   bool ao_reset = false;      // the next tracing launch carries RT_AO_LW_RESET
   uint32_t ao_n = 0;          // samples queued since the last reset: the counts' N once they ran
   rt_ao_params_t ao_params{};
+  // caller-supplied rays (vx_rt.h rt_query_reserve / rt_query_trace_start / rt_query_keys_start): the
+  // rt_query and rt_query_keys images, loaded and kept the same way, and the one buffer of the reserve
+  // (rt_common.h rt_query_arg_t: rays, hits, skip words, permutation and keys, 52 B per ray) -- kept
+  // across configures, with its argument area
+  vx_buffer_h q_img = nullptr, q_keys_img = nullptr, q_buf = nullptr;
+  uint64_t q_cap = 0;        // rays reserved; 0: no reserve
+  bool q_pending = false;    // a query launch was started and no wait has returned since
+  float q_box[6] = {0, 0, 0, 0, 0, 0};  // the key grid's box: the geometry corners' bounds
   vx_buffer_h nodes = nullptr, nodes4 = nullptr, tris = nullptr, layers = nullptr, dcs = nullptr, tex = nullptr;
   vx_buffer_h ptris = nullptr, geom = nullptr, oms = nullptr, bbox = nullptr, zbuf = nullptr;
   vx_buffer_h order = nullptr;
@@ -270,7 +278,8 @@ struct rt_renderer {
                            &cbuf, &cbuf1, &args, &verts, &pdc, &dcz, &layer_list, &geometry_list, &vis,
                            &blist, &bidx, &btrim, &btidx, &btrim_img, &btrim_args, &cdesc, &bglayer, &sidx, &slist, &pathq, &pathq_ctr, &oidx, &olist, &ovtris,
                            &accum, &aov, &aov_img, &relight_base, &aov_base_img, &relight_img,
-                           &dn_guide_img, &dn_prep_img, &dn_pass_img, &dn_buf, &ao_img, &ao_resolve_img, &ao_buf};
+                           &dn_guide_img, &dn_prep_img, &dn_pass_img, &dn_buf, &ao_img, &ao_resolve_img, &ao_buf,
+                           &q_img, &q_keys_img, &q_buf};
     for (auto* b : bufs) {
       if (*b) vx_mem_free(*b);
       *b = nullptr;

@@ -532,6 +532,77 @@ static inline uint32_t rt_ao_relight_mix(uint32_t base, uint32_t O, uint32_t W, 
   }
   return out;
 }
+// Caller-supplied rays against the scene's tree (vx_rt.h rt_query_reserve / rt_query_trace_start /
+// rt_query_keys_start).  The tracing launch (rt_query_kernel.hip, image rt_query) reads rt_ray_t records
+// (32 B: o[3], tmin, d[3], tmax) and stores one rt_hit_t (8 B: pid, t) per ray; the key launch
+// (rt_query_keys_kernel.hip, image rt_query_keys) stores one coherence key per ray.  Their argument area,
+// behind the eight above, which stay where they are: written by rt_query_reserve in stream order, constant
+// until the next reserve -- a configure does not touch it.
+typedef struct {
+  uint64_t rays_addr;   // rt_ray_t [capacity]
+  uint64_t hits_addr;   // rt_hit_t [capacity]
+  uint64_t skip_addr;   // int32 [capacity]: the primitive a ray does not meet (RT_QUERY_SKIP)
+  uint64_t perm_addr;   // uint32 [capacity]: slot -> ray index (RT_QUERY_PERM)
+  uint64_t keys_addr;   // uint32 [capacity]: the coherence keys
+  uint32_t capacity;    // rays reserved
+  uint32_t pad;
+  float key_lo[3];      // the key grid: the scene box's low corner ...
+  float key_inv[3];     // ... and 128 / its extent per axis (0 for a flat axis)
+} rt_query_arg_t;
+#define RT_QUERY_ARG_OFFSET (RT_AO_ARG_OFFSET + sizeof(rt_ao_arg_t))
+// A query launch's words: w[0] = n, the rays of the launch; w[1] = the mode (bits 0-7: RT_QUERY_CLOSEST /
+// RT_QUERY_ANY) and the flags (bits 8-15: RT_QUERY_SKIP / RT_QUERY_PERM as vx_rt.h numbers them, shifted);
+// w[2] = w[3] = 0 (a frame's light bits: none)
+#define RT_QUERY_LW_MODE_MASK 0xffu
+#define RT_QUERY_LW_FLAG_SHIFT 8
+#define RT_QUERY_MISS_KEY 0xffffffffu
+// A malformed ray (vx_rt.h): any of its 8 words NaN, an infinite origin or direction component, or an
+// all-zero direction.  w = the record's words: o[3], tmin, d[3], tmax.
+#if defined(__HIPCC__)
+__host__ __device__
+#endif
+static inline int rt_query_malformed(const uint32_t w[8]) {
+  int bad = 0, zero = 1;
+  for (int k = 0; k < 8; ++k) {
+    const uint32_t m = w[k] & 0x7fffffffu;
+    bad |= m > 0x7f800000u;                            // NaN
+    if (k != 3 && k != 7) bad |= m == 0x7f800000u;     // o, d: infinite
+    if (k >= 4 && k < 7) zero &= m == 0u;              // d: +-0
+  }
+  return bad | zero;
+}
+// The spread of a 7-bit cell index to every third bit (Morton interleave)
+#if defined(__HIPCC__)
+__host__ __device__
+#endif
+static inline uint32_t rt_query_part3(uint32_t c) {
+  uint32_t r = 0;
+  for (int b = 0; b < 7; ++b) r |= ((c >> b) & 1u) << (3 * b);
+  return r;
+}
+// The coherence key of a ray (vx_rt.h has the definition; every operation binary32, none fused -- each is a
+// single rounding, so host and device agree bit for bit)
+#if defined(__HIPCC__)
+__host__ __device__
+#endif
+static inline uint32_t rt_query_key_of(const uint32_t w[8], const float lo[3], const float inv[3]) {
+  if (rt_query_malformed(w)) return RT_QUERY_MISS_KEY;
+  float o[3], a[3];
+  uint32_t key = 0;
+  for (int k = 0; k < 3; ++k) {
+    const uint32_t ow = w[k], aw = w[4 + k] & 0x7fffffffu;
+    __builtin_memcpy(&o[k], &ow, 4);
+    __builtin_memcpy(&a[k], &aw, 4);
+    key |= (w[4 + k] >> 31) << (31 - k);
+    const float g = (o[k] - lo[k]) * inv[k];   // (inf * 0 on a flat axis is NaN: fmaxf returns the 0)
+    const uint32_t c = (uint32_t)__builtin_fminf(__builtin_fmaxf(g, 0.0f), 127.0f);
+    key |= rt_query_part3(c) << (8 + k);
+  }
+  const float s = (a[0] + a[1]) + a[2];        // > 0; +inf when it overflows: both cells 0 then
+  const uint32_t cx = (uint32_t)__builtin_fminf((a[0] / s) * 16.0f, 15.0f);
+  const uint32_t cy = (uint32_t)__builtin_fminf((a[1] / s) * 16.0f, 15.0f);
+  return key | (cy << 4) | cx;
+}
 // A path-traced frame lit by several point lights (pt_kernel.hip PT_LIGHTS, images pt_lights /
 // pt_lights_accum; vx_rt.h rt_renderer_set_path_lights) reads the first count <=
 // RT_MAX_PATH_LIGHTS entries of the same table, every one with lists (slist_on 1).  The cap is

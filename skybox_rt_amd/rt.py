@@ -103,6 +103,19 @@ class AoParams(C.Structure):
     _fields_ = [("radius", C.c_float), ("seed", C.c_uint32)]
 
 
+# caller-supplied rays (vx_rt.h rt_ray_t / rt_hit_t / rt_query_buffers_t, RT_QUERY_*)
+RAY_DTYPE = np.dtype([("o", "<f4", 3), ("tmin", "<f4"), ("d", "<f4", 3), ("tmax", "<f4")])
+HIT_DTYPE = np.dtype([("pid", "<i4"), ("t", "<f4")])
+QUERY_MODES = {"closest": 0, "any": 1}
+RT_QUERY_SKIP, RT_QUERY_PERM = 0x1, 0x2
+RT_QUERY_MISS_KEY = 0xFFFFFFFF
+
+
+class QueryBuffers(C.Structure):
+    _fields_ = [("rays", C.c_void_p), ("hits", C.c_void_p), ("skip", C.c_void_p), ("perm", C.c_void_p),
+                ("keys", C.c_void_p), ("capacity", C.c_uint64), ("box", C.c_float * 6)]
+
+
 class RenderParams(C.Structure):
     _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("flags", C.c_uint32),
                 ("light", C.c_float * 3), ("clear_color", C.c_uint32),
@@ -212,6 +225,17 @@ def lib():
             "rt_read_ao": [vp, vp, u64],
             "rt_render_ao_resolve_start": [vp, u32, vp, u32],
             "rt_render_ao_resolve": [vp, u32, vp, u32],
+            "rt_query_reserve": [vp, u64],
+            "rt_query_buffers": [vp, C.POINTER(QueryBuffers)],
+            "rt_query_write_rays": [vp, vp, u64, u64],
+            "rt_query_write_skip": [vp, vp, u64, u64],
+            "rt_query_write_perm": [vp, vp, u64, u64],
+            "rt_query_trace_start": [vp, u64, u32, u32],
+            "rt_query_trace": [vp, u64, u32, u32],
+            "rt_query_keys_start": [vp, u64],
+            "rt_query_keys": [vp, u64],
+            "rt_query_read_hits": [vp, vp, u64, u64],
+            "rt_query_read_keys": [vp, vp, u64, u64],
         }
         for name, argtypes in sig.items():
             fn = getattr(h, name)
@@ -229,6 +253,8 @@ def lib():
         h.rt_relight_resolve.restype = u32
         h.rt_ao_resolve.argtypes = [u32, u32, u32]
         h.rt_ao_resolve.restype = u32
+        h.rt_query_key.argtypes = [vp, C.POINTER(C.c_float)]
+        h.rt_query_key.restype = u32
         h.rt_last_error.restype = C.c_char_p
         h.rt_last_error.argtypes = []
         _h = h
@@ -387,6 +413,7 @@ class Renderer:
                                         C.byref(h)), "rt_renderer_create")
         self._h = h
         self.params = None
+        self._query_keep = []   # the tensors whose queued copies trace_rays() / query_keys() started
         # the tree rt_renderer_create built: on the device (binned SAH, the
         # host build's arrays) unless env RT_BVH=host
         st = self.bvh_stats()
@@ -760,6 +787,130 @@ class Renderer:
         fn = lib().rt_render_ao_resolve if wait else lib().rt_render_ao_resolve_start
         _check(fn(self._h, AO_MODES[mode], wp, n), "rt_render_ao_resolve" if wait else "rt_render_ao_resolve_start")
 
+    # caller-supplied rays (vx_rt.h rt_query_reserve; images rt_query, rt_query_keys)
+    def query_reserve(self, n: int) -> None:
+        """Reserve the device buffers for up to n rays per trace_rays() / query_keys()
+        call (52 B per ray).  The renderer must be configured; the reserve survives
+        configure(), set_light() and set_lights()."""
+        _check(lib().rt_query_reserve(self._h, int(n)), "rt_query_reserve")
+
+    def query_buffers(self) -> dict:
+        """The reserve's device pointers (rays, hits, skip, perm, keys), its capacity
+        in rays and the key grid's box float32[6] (lo.xyz, hi.xyz)."""
+        b = QueryBuffers()
+        _check(lib().rt_query_buffers(self._h, C.byref(b)), "rt_query_buffers")
+        out = {k: getattr(b, k) for k in ("rays", "hits", "skip", "perm", "keys")}
+        out["capacity"] = int(b.capacity)
+        out["box"] = np.array(list(b.box), np.float32)
+        return out
+
+    def _query_upload(self, what: str, rays, skip):
+        """rays (and skip) into the reserve, rays converted to rt_ray_t -> (n, on_device)"""
+        n, dev = _query_check(what, rays, skip)
+        if dev:
+            import torch
+            ext = torch.cuda.ExternalStream(self.device_stream())
+            buf = self.query_buffers()
+            if n > buf["capacity"]:
+                raise RtError(f"{what} failed: {n} rays is above the reserve's capacity of {buf['capacity']}")
+            ext.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(ext):
+                conv = rays[:, list(_RAY_COLUMNS)].contiguous()
+                keep = [conv]
+                _hip_copy(buf["rays"], conv.data_ptr(), 32 * n, ext.cuda_stream)
+                if skip is not None:
+                    sk = skip.contiguous()
+                    keep.append(sk)
+                    _hip_copy(buf["skip"], sk.data_ptr(), 4 * n, ext.cuda_stream)
+            self._query_keep = keep   # (alive until the next call: the copies are queued, not done)
+            return n, True
+        conv = np.ascontiguousarray(rays[:, list(_RAY_COLUMNS)])
+        _check(lib().rt_query_write_rays(self._h, conv.ctypes.data, 0, n), "rt_query_write_rays")
+        if skip is not None:
+            sk = np.ascontiguousarray(skip)
+            _check(lib().rt_query_write_skip(self._h, sk.ctypes.data, 0, n), "rt_query_write_skip")
+        return n, False
+
+    def _query_keys_device(self, n: int):
+        """the keys of rays [0, n) as an int64 tensor (0 .. 2^32 - 1), on the renderer's stream"""
+        import torch
+        ext = torch.cuda.ExternalStream(self.device_stream())
+        buf = self.query_buffers()
+        with torch.cuda.stream(ext):
+            raw = torch.empty(n, dtype=torch.int32, device="cuda")
+            _hip_copy(raw.data_ptr(), buf["keys"], 4 * n, ext.cuda_stream)
+            keys = raw.to(torch.int64) & 0xFFFFFFFF
+        return keys, ext
+
+    def query_keys(self, rays, wait: bool = True):
+        """The coherence keys (vx_rt.h rt_query_key) of rays float32 [n, 8] in the
+        oracle's column order (o, d, tmin, tmax), computed on the device: uint32 [n]
+        for an array, an int64 tensor for a CUDA tensor."""
+        n, dev = self._query_upload("rt_query_keys", rays, None)
+        _check(lib().rt_query_keys_start(self._h, n), "rt_query_keys_start")
+        if dev:
+            import torch
+            keys, ext = self._query_keys_device(n)
+            torch.cuda.current_stream().wait_stream(ext)
+            if wait:
+                ext.synchronize()
+                _check(lib().rt_render_wait(self._h), "rt_render_wait")
+            return keys
+        out = np.zeros(n, np.uint32)
+        _check(lib().rt_query_read_keys(self._h, out.ctypes.data, 0, n), "rt_query_read_keys")
+        return out
+
+    def trace_rays(self, rays, mode: str = "closest", skip=None, sort: bool = False, wait: bool = True):
+        """Trace rays float32 [n, 8] in the oracle's column order (o, d, tmin, tmax;
+        clip (x, y, w) space, the space of Scene.prims()[:, :, (0, 1, 3)]) against
+        the scene's geometry: mode "closest" the nearest hit (lowest pid on ties),
+        "any" some occluder (rely on pid >= 0 only).  skip: int32 [n], the primitive
+        a ray does not meet, -1 for none.  sort=True traces the rays in the order of
+        their coherence keys (one more launch and a sort; the hits stay at the rays'
+        own indices).  -> (pid int32 [n], t float32 [n]); a miss is (-1, 0.0).  A
+        CUDA torch tensor is taken as it is on the renderer's stream and the hits
+        come back as tensors.  wait=False returns None once the launch is queued:
+        query_hits(n) reads the hits later."""
+        if mode not in QUERY_MODES:
+            raise RtError(f"rt_query_trace failed: mode is one of {sorted(QUERY_MODES)}")
+        n, dev = self._query_upload("rt_query_trace", rays, skip)
+        flags = RT_QUERY_SKIP if skip is not None else 0
+        if sort:
+            _check(lib().rt_query_keys_start(self._h, n), "rt_query_keys_start")
+            flags |= RT_QUERY_PERM
+            if dev:
+                import torch
+                keys, ext = self._query_keys_device(n)
+                with torch.cuda.stream(ext):
+                    perm = torch.sort(keys, stable=True).indices.to(torch.int32)
+                    _hip_copy(self.query_buffers()["perm"], perm.data_ptr(), 4 * n, ext.cuda_stream)
+                self._query_keep.append(perm)
+            else:
+                keys = np.zeros(n, np.uint32)
+                _check(lib().rt_query_read_keys(self._h, keys.ctypes.data, 0, n), "rt_query_read_keys")
+                perm = np.ascontiguousarray(np.argsort(keys, kind="stable"), np.uint32)
+                _check(lib().rt_query_write_perm(self._h, perm.ctypes.data, 0, n), "rt_query_write_perm")
+        _check(lib().rt_query_trace_start(self._h, n, QUERY_MODES[mode], flags), "rt_query_trace_start")
+        if dev:
+            import torch
+            ext = torch.cuda.ExternalStream(self.device_stream())
+            with torch.cuda.stream(ext):
+                hits = torch.empty((n, 2), dtype=torch.int32, device="cuda")
+                _hip_copy(hits.data_ptr(), self.query_buffers()["hits"], 8 * n, ext.cuda_stream)
+            torch.cuda.current_stream().wait_stream(ext)
+            if wait:
+                ext.synchronize()
+                _check(lib().rt_render_wait(self._h), "rt_render_wait")
+            return hits[:, 0], hits[:, 1].view(torch.float32)
+        return self.query_hits(n) if wait else None
+
+    def query_hits(self, n: int):
+        """The hits of rays [0, n) of the last trace_rays(): (pid int32 [n], t
+        float32 [n]) (waits for the device)."""
+        out = np.zeros(int(n), HIT_DTYPE)
+        _check(lib().rt_query_read_hits(self._h, out.ctypes.data, 0, int(n)), "rt_query_read_hits")
+        return out["pid"].copy(), out["t"].copy()
+
     # denoising accumulated path frames (vx_rt.h rt_denoise_capture_start; images rt_aov_guide,
     # rt_denoise_prep, rt_denoise_pass)
     def denoise_capture(self, wait: bool = True) -> None:
@@ -978,6 +1129,78 @@ def ao_resolve(argb, occluded, n: int):
     uniq, inv = np.unique(key.reshape(-1), return_inverse=True)
     vals = np.array([fn(int(u >> np.uint64(32)), int(u & np.uint64(0xFFFFFFFF)), int(n)) for u in uniq], np.uint32)
     return vals[inv.reshape(-1)].reshape(a.shape)
+
+
+# the oracle's ray row (o, d, tmin, tmax) -> rt_ray_t (o, tmin, d, tmax)
+_RAY_COLUMNS = (0, 1, 2, 6, 3, 4, 5, 7)
+
+
+def _is_tensor(a) -> bool:
+    return hasattr(a, "is_cuda") and hasattr(a, "data_ptr")
+
+
+def _query_check(what: str, rays, skip):
+    """shapes and dtypes of a ray table and its skip words, before any device call
+    -> (n, whether they are CUDA tensors)"""
+    dev = _is_tensor(rays)
+    if dev:
+        import torch
+        if not rays.is_cuda or rays.dtype != torch.float32:
+            raise RtError(f"{what} failed: a ray tensor is float32 on a CUDA device")
+    elif not isinstance(rays, np.ndarray) or rays.dtype != np.float32:
+        raise RtError(f"{what} failed: rays are a float32 array (or CUDA tensor) [n, 8]")
+    if rays.ndim != 2 or rays.shape[1] != 8 or rays.shape[0] == 0:
+        raise RtError(f"{what} failed: rays are [n, 8] (o, d, tmin, tmax), n >= 1; got {tuple(rays.shape)}")
+    n = int(rays.shape[0])
+    if skip is not None:
+        if _is_tensor(skip) != dev:
+            raise RtError(f"{what} failed: skip is an array with array rays, a CUDA tensor with tensor rays")
+        if dev:
+            import torch
+            ok = skip.is_cuda and skip.dtype == torch.int32
+        else:
+            ok = isinstance(skip, np.ndarray) and skip.dtype == np.int32
+        if not ok or skip.ndim != 1 or skip.shape[0] != n:
+            raise RtError(f"{what} failed: skip is int32 [n], one word per ray")
+    return n, dev
+
+
+_hip = None
+
+
+def _hip_copy(dst: int, src: int, nbytes: int, stream: int) -> None:
+    """hipMemcpyAsync device to device on `stream` (torch's HIP runtime, which the
+    driver shares: _lib loads torch first)"""
+    global _hip
+    if _hip is None:
+        h = C.CDLL("libamdhip64.so.7")
+        h.hipMemcpyAsync.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]
+        h.hipMemcpyAsync.restype = C.c_int
+        _hip = h
+    rc = _hip.hipMemcpyAsync(dst, src, nbytes, 3, stream)  # hipMemcpyDeviceToDevice
+    if rc != 0:
+        raise RtError(f"hipMemcpyAsync failed ({rc})")
+
+
+def query_key(ray, box):
+    """rt_query_key: the coherence key of a ray float32 [8] in the oracle's column
+    order (o, d, tmin, tmax) over box float32 [6] (lo.xyz, hi.xyz) -> int; rows
+    [n, 8] -> uint32 [n]."""
+    r = np.ascontiguousarray(np.asarray(ray, np.float32))
+    b = (C.c_float * 6)(*[float(v) for v in np.asarray(box, np.float32).reshape(6)])
+    if r.ndim == 1 and r.shape[0] != 8:
+        raise RtError("rt_query_key failed: a ray is 8 floats (o, d, tmin, tmax)")
+    if r.ndim not in (1, 2) or r.shape[-1] != 8:
+        raise RtError("rt_query_key failed: rays are [n, 8] (o, d, tmin, tmax)")
+    fn = lib().rt_query_key
+    if r.ndim == 1:
+        c = np.ascontiguousarray(r[list(_RAY_COLUMNS)])
+        return int(fn(c.ctypes.data, b))
+    c = np.ascontiguousarray(r[:, list(_RAY_COLUMNS)])
+    base, out = c.ctypes.data, np.zeros(len(c), np.uint32)
+    for i in range(len(c)):
+        out[i] = fn(base + 32 * i, b)
+    return out
 
 
 def path_lights_resolve(sums, k: int, alpha_argb: int) -> int:
