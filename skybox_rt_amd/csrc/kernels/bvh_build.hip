@@ -391,8 +391,9 @@ __device__ void phase_emit(const bvh_build_arg_t* a) {
         lo = make_float4(fminf(lo.x, l.x), fminf(lo.y, l.y), fminf(lo.z, l.z), 0.0f);
         hi = make_float4(fmaxf(hi.x, h.x), fmaxf(hi.y, h.y), fmaxf(hi.z, h.z), 0.0f);
       }
+      // the array holds n - 1 records; the ones behind the root are reached by nothing and zero
       float* nd = nodes[0].v;
-      for (int q = 0; q < 16; ++q) nd[q] = 0.0f;
+      for (int q = 0; q < 16 * (n > 1 ? n - 1 : 1); ++q) nd[q] = 0.0f;
       set_child(nd, 0, lo, hi, pad, (int32_t)(RT_LEAF_FLAG | (uint32_t)(n - 1)));
       set_child(nd, 1, lo, hi, pad, RT_EMPTY_REF);
       atomicMax(&bounds[7], 1u);

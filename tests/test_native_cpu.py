@@ -7,11 +7,15 @@ import ctypes as C
 import os
 import re
 import subprocess
+import sys
 
 import numpy as np
 import pytest
 
 from conftest import ROOT, scene_path
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import bvh_reference as br  # noqa: E402
 
 os.environ.setdefault("SKYBOX_RT_NO_TORCH", "1")
 
@@ -104,31 +108,15 @@ def test_fixed_point_setup_matches_oracle(oracle_lib, name, size):
             assert got[g, 30] == dci
 
 
-def _check_bvh(nodes, tris, npids):
-    seen = []
+def _corners(s):
+    """every primitive's clip (x, y, w) corners by pid (float32[P, 3, 3])"""
+    return np.ascontiguousarray(s.prims()[:, :, [0, 1, 3]], np.float32)
 
-    def walk(ref, lo, hi, depth):
-        if ref >= 0:
-            n = nodes[ref]
-            for ch in range(2):
-                c = int(n[12:14].view(np.int32)[ch])
-                if c == -1:
-                    continue
-                clo = n[[0 + 2 * ch, 4 + 2 * ch, 8 + 2 * ch]]
-                chi = n[[1 + 2 * ch, 5 + 2 * ch, 9 + 2 * ch]]
-                assert np.all(clo <= chi)
-                walk(c, clo, chi, depth + 1)
-        else:
-            u = ref & 0xFFFFFFFF
-            first, count = (u >> 4) & 0x7FFFFFF, (u & 15) + 1
-            for k in range(first, first + count):
-                t = tris[k]
-                v0, e1, e2 = t[0:3], t[4:7], t[8:11]
-                for p in (v0, v0 + e1, v0 + e2):   # vertices inside the padded box
-                    assert np.all(p >= lo - 1e-3) and np.all(p <= hi + 1e-3)
-                seen.append(int(t[3:4].view(np.int32)[0]))
-    walk(0, None, None, 0)
-    assert sorted(seen) == sorted(npids)
+
+def _check_bvh(s, nodes, tris, pids):
+    """tests/bvh_reference.py check_bvh2: every pid of `pids` in exactly one leaf slot, leaves of
+    1..4, every record its triangle bit for bit, corners and child boxes contained exactly"""
+    return br.check_bvh2(nodes, tris, _corners(s), pids=pids)
 
 
 @pytest.mark.parametrize("name", ["tekkaman", "scene", "box", "vase"])
@@ -141,7 +129,7 @@ def test_bvh_structure(name):
     geom = [g for g in range(info["num_prims"])]
     ref_pids = sorted(int(x) for x in tris[:, 3].view(np.int32))
     assert len(set(ref_pids)) == len(ref_pids)
-    _check_bvh(nodes, tris, ref_pids)
+    assert _check_bvh(s, nodes, tris, ref_pids) == info["bvh_depth"]
     assert set(ref_pids) <= set(geom)
 
 
@@ -160,43 +148,14 @@ def test_bvh_traversal_equals_bruteforce(oracle_lib, name, size, shadows):
     assert kv["tri_tests"] < kb["tri_tests"]
 
 
-def _check_bvh4(nodes4, nodes, tris, stack_bound):
-    """The 4-wide BVH holds exactly the BVH2's leaves, under the same padded
-    boxes, and the host's stack bound covers every root-to-leaf walk."""
-    leaves4, leaves2 = [], []
-
-    def walk2(ref):
-        if ref >= 0:
-            for ch in range(2):
-                c = int(nodes[ref][12:14].view(np.int32)[ch])
-                if c != -1:
-                    walk2(c)
-        else:
-            leaves2.append(ref)
-
-    def walk4(ref, lo, hi):
-        n = nodes4[ref]
-        refs = n[24:28].view(np.int32)
-        used = [i for i in range(4) if refs[i] != -1]
-        assert used == list(range(len(used))) and (len(used) >= 2 or ref == 0)
-        need = 0
-        for i in used:
-            clo = n[[i, 8 + i, 16 + i]]
-            chi = n[[4 + i, 12 + i, 20 + i]]
-            assert np.all(clo <= chi)
-            if lo is not None:                      # BVH2 nesting: child box inside parent's
-                assert np.all(clo >= lo - 1e-3) and np.all(chi <= hi + 1e-3)
-            c = int(refs[i])
-            if c >= 0:
-                need = max(need, walk4(c, clo, chi))
-            else:
-                leaves4.append(c)
-        return len(used) - 1 + need
-
-    walk2(0)
-    st = walk4(0, None, None)
-    assert sorted(leaves4) == sorted(leaves2)
+def _check_bvh4(s, nodes4, nodes, tris, stack_bound, f16):
+    """tests/bvh_reference.py check_bvh4: the 4-wide BVH holds exactly the BVH2's leaves, every
+    corner and child box contained exactly, used slots first, and the stack bound is the worst
+    root-to-leaf walk's; with f16 every plane is a binary16 value"""
+    pids = tris[:, 3].copy().view(np.int32)
+    depth4, st = br.check_bvh4(nodes4, nodes, tris, _corners(s), f16=f16, pids=pids)
     assert st == stack_bound
+    return depth4
 
 
 @pytest.mark.parametrize("name", ["tekkaman", "scene", "box", "carnival"])
@@ -210,7 +169,7 @@ def test_bvh4_collapse_structure(name):
     if len(nodes) > 100:
         # each BVH4 node absorbs up to 3 BVH2 nodes (about half of them in practice)
         assert len(nodes4) <= 0.6 * len(nodes) and info["bvh4_depth"] < info["bvh_depth"]
-    _check_bvh4(nodes4, nodes, tris, info["bvh4_stack"])
+    assert _check_bvh4(s, nodes4, nodes, tris, info["bvh4_stack"], f16=True) == info["bvh4_depth"]
     assert info["bvh4_stack"] <= 32
 
 
@@ -293,7 +252,7 @@ def test_lbvh_collapse4_oracle_structure_and_traversal(oracle_lib, name):
     verts, geom, _ = lbvh_inputs(s)
     nodes, tris, depth = po.lbvh_build(verts, geom)
     nodes4, stack = po.lbvh_collapse4(nodes)
-    _check_bvh4(nodes4, nodes, tris, stack)
+    _check_bvh4(s, nodes4, nodes, tris, stack, f16=False)
     assert stack <= 3 * ((depth + 1) // 2)
     osc = po.OracleScene(po.cgltrace.load(scene_path(name)))
     p = po.rt_params(160, 160, shadows=True, nthreads=8)
@@ -314,7 +273,7 @@ def test_lbvh_oracle_structure_and_traversal(oracle_lib, name):
     verts, geom, pids = lbvh_inputs(s)
     nodes, tris, depth = po.lbvh_build(verts, geom)
     assert 1 <= depth <= 32
-    _check_bvh(nodes, tris, sorted(int(p) for p in pids))
+    assert _check_bvh(s, nodes, tris, pids) == depth
     osc = po.OracleScene(po.cgltrace.load(scene_path(name)))
     p = po.rt_params(160, 160, shadows=True, nthreads=8)
     cb, pb, tb, _ = po.rt_render(osc, p)
