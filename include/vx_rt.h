@@ -895,6 +895,111 @@ int rt_query_read_keys(rt_renderer_h r, uint32_t* out, uint64_t first, uint64_t 
 /* a ray's key restated on the host */
 uint32_t rt_query_key(const rt_ray_t* ray, const float box[6]);
 
+/* Soft shadows from area lights, sampled on the device from a frame's
+ * visibility records.  NO REFERENCE (the definition below composes routines
+ * that are pinned already; tests/soft_reference.py restates it from the
+ * oracle's primitives and the device is held to that bit for bit).
+ *
+ * Framebuffer, pixel index p, rec[p] and "ray pixel" are the ambient-occlusion
+ * block's above: linear W x H only; (depth_flags & RT_AOV_GEOM) and t > 0 && t
+ * < +inf; RT_AOV_SHADOW_RAY is not read.
+ * Lights.  The n lights in use when the session begins, by the relight
+ * capture's rule: 1 after rt_renderer_configure or rt_renderer_set_light, k
+ * after rt_renderer_set_lights.  Light i has its position L_i and a radius R_i,
+ * a finite float >= 0.
+ * A ray pixel's sample c -- the 0-based cursor since rt_renderer_soft_begin or
+ * rt_renderer_soft_reset -- has one ray per light i, computed in binary32,
+ * every operation a single one in the order written, fused only where fmaf is
+ * written:
+ *   1. P = d * (t * 0.999755859375f), d the pixel's primary direction (the
+ *      ambient-occlusion block's P, the frames' shadow origin);
+ *   2. m_k = P_k - L_i,k;
+ *   3. len = sqrtf(dot3(m, m)) (dot3 as kernels/rt_trace.h: fmaf(m2, m2,
+ *      fmaf(m1, m1, m0 * m0)));
+ *   4. if len is 0 or not finite the sample is not occluded and walks nothing;
+ *   5. m_k = m_k / len;
+ *   6. u = bounce_dir(m, pt_key(seed + c mod 2^32, p, 64 + i)) (kernels/
+ *      rt_path.h; the oracle's pt_bounce_dir): a cosine-weighted point of the
+ *      unit hemisphere about m -- the side of the light's sphere that faces P,
+ *      uniform over its projected disc.  Vertex index 64 + i keeps these
+ *      streams apart from the path tracer's and ambient occlusion's;
+ *   7. target_k = fmaf(R_i, u_k, L_i,k);
+ *   8. the ray has origin P and direction target - P; it is occluded iff some
+ *      geometry triangle other than pid meets it (Moeller-Trumbore as the
+ *      frames' rays) at 0 < t < 1.  The verdict does not depend on traversal
+ *      order.
+ * With R_i = 0 the target is L_i exactly, and every sample's verdict is the
+ * frame's own hard-shadow verdict for that light (the record's light_mask bit).
+ * Record.  One uint16 per (light, pixel), stored as planes: index i * W * H + p;
+ * the occluded samples so far, 0 for a pixel that is not a ray pixel.  N, the
+ * sample cursor, is the renderer's, and N <= 1024.
+ * Resolve.  rt_soft_resolve(base_argb, depth_flags, counts[n], N, weights[n],
+ * n): w_i in 0..255, D = N * sum w_i, O = sum w_i * o_i with o_i clamped to N.
+ * A pixel with RT_AOV_GEOM (a ray pixel's counts; any other pixel's are 0) is
+ * per colour channel c of the base colour (2 * ((D - O) * c + O * (c >> 1)) +
+ * D) / (2 * D) in integer division, under the base colour's alpha byte; any
+ * other pixel is its base colour.  base_argb is returned unchanged when N = 0,
+ * N > 1024, n is outside 1..RT_MAX_LIGHTS or sum w_i = 0.
+ *   - N <= 1024 keeps the numerator, at most 2 * 255 * D + D = 511 * D <= 511 *
+ *     1024 * (16 * 255 = 4080) = 2 134 917 120, below 2^32: uint32 arithmetic
+ *     suffices on the host and on the device.
+ *   - When every o_i is 0 or N, O = N * O' with O' the sum of the weights of
+ *     the lights at N, and D = N * W: numerator 2 * N * ((W - O') * c + O' * (c
+ *     >> 1)) + N * W and denominator 2 * N * W both carry the factor N, so the
+ *     value is rt_relight_resolve's under the mask of the lights at N.
+ *
+ * rt_renderer_soft_begin(r, params): valid where rt_renderer_ao_begin is, with
+ * its refusals (-2, rt_last_error says why), and refused too when n is not the
+ * count of lights in use, when a radius is NaN, negative or infinite, or when
+ * the arena cannot hold the planes' n * W * H * 2 B; a refused begin changes
+ * nothing: a session already begun goes on.  It allocates the planes
+ * (rt_renderer_configure and rt_renderer_free release them and end the
+ * session), loads rt_soft.vxbin and rt_soft_resolve.vxbin (the kernel
+ * directory's, else the library's) on the first call, and writes the launch's
+ * argument area -- planes, radii, the lights' positions -- in stream order; the
+ * next tracing launch resets.  rt_renderer_set_light, rt_renderer_set_lights
+ * and rt_renderer_set_path_lights end the session, unlike an ambient-occlusion
+ * session: the counts describe other lights.
+ * rt_renderer_soft_reset: the cursor back to 0, the next launch resets -- no
+ * clearing launch and no copy, the reset travels in the launch words.
+ *
+ * rt_render_soft_start(r, samples): one launch of rt_soft (kernels/
+ * rt_soft_kernel.hip) tracing samples = 1..64 rays per ray pixel and light,
+ * with no host wait and no copy; -2 for samples out of range or a cursor that
+ * would pass 1024.  An ordinary launch as an ambient-occlusion launch is.  It
+ * writes only the planes; with RT_RENDER_COUNTERS rt_render_stats after it
+ * gives shadow_rays = the rays traced and occluded = the sum of their verdicts
+ * (every other counter 0).
+ *
+ * rt_render_soft_resolve_start(r, mode, weights, n): one launch of
+ * rt_soft_resolve (kernels/rt_soft_resolve_kernel.hip), a streaming pass into
+ * the framebuffer in use, as a relight launch goes.  RT_SOFT_LIT needs a live
+ * relight capture (rt_render_relight_start's rule) and writes rt_soft_resolve(
+ * base, depth_flags, counts, N, weights, n); weights NULL means unit weights.
+ * RT_SOFT_GREY takes base 0xffffffff and unit weights and needs no capture.  -2
+ * for N = 0, an unknown mode, n not the session's count (with weights), every
+ * weight 0. */
+typedef struct {
+  const float* radii;   /* n radii, each finite and >= 0 */
+  uint32_t n;           /* the lights in use */
+  uint32_t seed;        /* sample c is keyed by seed + c */
+} rt_soft_params_t;
+#define RT_SOFT_DEFAULT_SEED 0x5EEDu   /* rtapp -E's, and the Python layer's default */
+#define RT_SOFT_LIT 0u
+#define RT_SOFT_GREY 1u
+int rt_renderer_soft_begin(rt_renderer_h r, const rt_soft_params_t* params);
+int rt_renderer_soft_reset(rt_renderer_h r);
+int rt_render_soft_start(rt_renderer_h r, uint32_t samples);
+int rt_render_soft(rt_renderer_h r, uint32_t samples);            /* start + wait */
+int rt_renderer_soft_samples(rt_renderer_h r, uint32_t* n);       /* the sample cursor N */
+/* the planes, light-major in framebuffer order, count >= lights * the framebuffer's pixels (waits for the device) */
+int rt_read_soft(rt_renderer_h r, uint16_t* out, uint64_t count);
+int rt_render_soft_resolve_start(rt_renderer_h r, uint32_t mode, const uint8_t* weights, uint32_t n);
+int rt_render_soft_resolve(rt_renderer_h r, uint32_t mode, const uint8_t* weights, uint32_t n);  /* start + wait */
+/* the resolved pixel restated on the host */
+uint32_t rt_soft_resolve(uint32_t base_argb, uint32_t depth_flags, const uint16_t* counts, uint32_t N,
+                         const uint8_t* weights, uint32_t n);
+
 /* Read back one per-resolution record array of the current configuration
  * (layouts: kernels/rt_common.h; NO REFERENCE).  out NULL = size query
  * (*size = bytes). */

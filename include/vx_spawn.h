@@ -153,6 +153,9 @@ struct vx_arena {
   __device__ __forceinline__ uint32_t ld_u8(uint32_t off) const {
     return __builtin_amdgcn_raw_buffer_load_b8(r, off, 0, 0);
   }
+  __device__ __forceinline__ void st_u16(uint32_t off, uint32_t v) const {
+    __builtin_amdgcn_raw_buffer_store_b16((uint16_t)v, r, off, 0, 0);
+  }
   __device__ __forceinline__ void st_u32(uint32_t off, uint32_t v) const {
     __builtin_amdgcn_raw_buffer_store_b32(v, r, off, 0, 0);
   }

@@ -34,7 +34,8 @@ REQUIRED = ("libvortex.so", "libvortex-hip.so", "librtapp.so", "rtapp",
             "pt_lights.vxbin", "pt_lights_accum.vxbin", "tex_kat.vxbin", "rt_aov.vxbin",
             "rt_aov_base.vxbin", "rt_relight.vxbin", "rt_kat.vxbin", "rt_kat_pt.vxbin",
             "rt_aov_guide.vxbin", "rt_denoise_prep.vxbin", "rt_denoise_pass.vxbin",
-            "rt_ao.vxbin", "rt_ao_resolve.vxbin", "rt_query.vxbin", "rt_query_keys.vxbin")
+            "rt_ao.vxbin", "rt_ao_resolve.vxbin", "rt_query.vxbin", "rt_query_keys.vxbin",
+            "rt_soft.vxbin", "rt_soft_resolve.vxbin")
 
 
 class NativeLibraryMissing(RuntimeError):

@@ -46,6 +46,13 @@
 // RT_AO_DEFAULT_SEED), then the modulate resolve (rt_render_ao_resolve) under
 // -W's weights, or unit weights -- the relit frame times the ambient term,
 // written to -o -- and one line "AO: <samples> samples, radius <r>";
+// -E samples[,radius]: with -S, after the frame a relight capture and that many
+// soft-shadow samples per ray pixel and light of -L / -M (rt_render_soft:
+// launches of 64, then one for the rest; every light a sphere of `radius`, by
+// default 1; seed RT_SOFT_DEFAULT_SEED), then the lit resolve
+// (rt_render_soft_resolve) under -W's weights, or unit weights -- the frame
+// with penumbrae, written to -o -- and one line "Soft: <samples> samples,
+// radius <r>" (not with -K);
 // multi-GPU (one process per GPU over
 // librt_shard.so / RCCL): -G rank,ranks -I idfile -- this process renders
 // 32x32 tiles t with t % ranks == rank, rank 0 writes the RCCL communicator
@@ -99,6 +106,7 @@ const char* aov_file = nullptr;       // -V: write the frame's visibility record
 const char* weights_arg = nullptr;    // -W: relight the frame under these per-light weights
 const char* denoise_arg = nullptr;    // -D: with -A, denoise the accumulated frame
 const char* ao_arg = nullptr;         // -K: with -S, the frame times its ambient occlusion
+const char* soft_arg = nullptr;       // -E: with -S, the frame under area lights
 
 #ifdef RT_APP_RASTER
 const char* kOpts = "t:i:o:r:w:h:k:n:z?";
@@ -108,7 +116,7 @@ void usage() {
               "[-k tilelogsize] [-n repeat]\n");
 }
 #else
-const char* kOpts = "t:s:e:i:o:r:w:h:k:n:L:M:P:G:I:B:A:V:W:D:K:uxyzSRFHO?";
+const char* kOpts = "t:s:e:i:o:r:w:h:k:n:L:M:P:G:I:B:A:V:W:D:K:E:uxyzSRFHO?";
 void usage() {
   std::printf("Vortex 3D Rendering Test (MI355X).\n"
               "Usage: [-t trace] [-s startdraw] [-e enddraw] [-o output] [-r reference] [-w width] "
@@ -122,6 +130,7 @@ void usage() {
               "       [-V file: the frame's per-pixel visibility records (primary + shadow frames)]\n"
               "       [-W w0,w1,...: with -S, relight the frame under one weight 0..255 per light of -L / -M]\n"
               "       [-K samples[,radius]: with -S, the relit frame times that many samples of ambient occlusion]\n"
+              "       [-E samples[,radius]: with -S, the frame's shadows from that many samples of lights of that radius]\n"
               "       env RT_KERNEL_DIR: kernel images; RT_ASSETS_PATHS: search directories\n");
 }
 #endif
@@ -173,6 +182,7 @@ int main(int argc, char** argv) {
     case 'W': weights_arg = optarg; break;
     case 'D': denoise_arg = optarg; break;
     case 'K': ao_arg = optarg; break;
+    case 'E': soft_arg = optarg; break;
 #endif
     case '?': usage(); return 0;
     default: usage(); return -1;  // -i: in the reference's option string, never handled
@@ -243,6 +253,17 @@ int main(int argc, char** argv) {
     const int got = std::sscanf(ao_arg, "%u,%f", &ao_samples, &ao.radius);
     if (!shadows || rank >= 0 || got < 1 || ao_samples < 1 || ao_samples > 65535u || !(ao.radius > 0.0f)) {
       std::printf("Error: -K samples[,radius] needs -S, one rank, 1..65535 samples and a positive radius\n");
+      usage();
+      return 1;
+    }
+  }
+  uint32_t soft_samples = 0;
+  float soft_radius = 1.0f;
+  if (soft_arg) {
+    const int got = std::sscanf(soft_arg, "%u,%f", &soft_samples, &soft_radius);
+    if (!shadows || rank >= 0 || ao_arg || got < 1 || soft_samples < 1 || soft_samples > 1024u ||
+        !(soft_radius >= 0.0f) || soft_radius == __builtin_inff()) {
+      std::printf("Error: -E samples[,radius] needs -S, one rank, no -K, 1..1024 samples and a finite radius >= 0\n");
       usage();
       return 1;
     }
@@ -450,6 +471,23 @@ int main(int argc, char** argv) {
     }
     RT_CHECK(rt_render_ao_resolve(r, RT_AO_MODULATE, weights.data(), (uint32_t)weights.size()));
     std::printf("AO: %u samples, radius %g\n", ao_samples, (double)ao.radius);
+  }
+  if (soft_arg) {
+    // the frame under area lights: the framebuffer written below
+    if (!weights_arg) {
+      weights.assign(more_lights.size() + 1, 1);
+      RT_CHECK(rt_relight_capture(r));
+    }
+    const std::vector<float> radii(weights.size(), soft_radius);
+    const rt_soft_params_t sp{radii.data(), (uint32_t)radii.size(), RT_SOFT_DEFAULT_SEED};
+    RT_CHECK(rt_renderer_soft_begin(r, &sp));
+    for (uint32_t left = soft_samples; left;) {
+      const uint32_t k = left < 64u ? left : 64u;
+      RT_CHECK(rt_render_soft_start(r, k));
+      left -= k;
+    }
+    RT_CHECK(rt_render_soft_resolve(r, RT_SOFT_LIT, weights.data(), (uint32_t)weights.size()));
+    std::printf("Soft: %u samples, radius %g\n", soft_samples, (double)soft_radius);
   }
   int errors = 0;
   if (std::strcmp(output_file, "null") != 0 && (!sharded || rank == 0)) {

@@ -14,6 +14,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <chrono>
+#include <cmath>
 #include <map>
 #include <cstring>
 #include <memory>
@@ -576,6 +577,7 @@ int rt_renderer_set_light(rt_renderer_h r, const float light[3]) {
   uint32_t launches = 0;
   r->nlights = 0;  // back to one light (rt_renderer_set_lights)
   r->relight_n = 0;  // a capture's masks describe the lights before (rt_relight_capture_start)
+  r->soft_on = false;  // and a soft-shadow session's counts (rt_renderer_soft_begin)
   if (rtapp::set_light(r, light, &launches) != 0) return -1;
   r->setup.slist_built = r->sl_mode ? 1u : 0u;
   // a moved light changes what the accumulated samples estimate: the next
@@ -634,6 +636,7 @@ int rt_renderer_set_lights(rt_renderer_h r, const float (*lights)[3], uint32_t n
   if (!r) return fail("null argument");
   if (!r->configured) return fail("renderer not configured");
   r->relight_n = 0;  // whatever becomes of the call, a capture's masks are not trusted past it
+  r->soft_on = false;  // nor a soft-shadow session's counts
   if (n < 1 || n > RT_MAX_LIGHTS) return fail("rt_renderer_set_lights: 1 to 16 lights", -2);
   if (!lights) return fail("null argument");
   const uint32_t f = r->params.flags;
@@ -707,6 +710,7 @@ int rt_renderer_set_path_lights(rt_renderer_h r, const float (*lights)[3], uint3
   // leaves the single light (as after rt_renderer_set_light), and accumulated samples start over
   r->nlights = 0;
   r->relight_n = 0;
+  r->soft_on = false;
   if (r->accum_on) {
     r->accum_reset = true;
     r->accum_n = 0;
@@ -1414,6 +1418,11 @@ int rt_renderer_configure(rt_renderer_h r, const rt_render_params_t* p) {
   r->ao_bytes = 0;
   r->ao_on = r->ao_reset = r->aov_launched = false;
   r->ao_n = 0;
+  // and the soft-shadow planes; the session is over
+  if (release_idle(r, &r->soft_buf) != 0) return -1;
+  r->soft_bytes = 0;
+  r->soft_on = r->soft_reset = false;
+  r->soft_n = r->soft_lights = 0;
   r->nlights = 0;  // a configure returns to one light (rt_renderer_set_lights)
   rt_kernel_arg_t& a = r->arg;
   a.width = p->width;
@@ -1656,8 +1665,9 @@ int rt_renderer_configure(rt_renderer_h r, const rt_render_params_t* p) {
   // (and the denoiser's area: rt_denoise_capture_start writes it)
   // (and the ambient-occlusion area: rt_renderer_ao_begin writes it)
   // (and the ray queries' area: rt_query_reserve writes it)
+  // (and the soft shadows' area: rt_renderer_soft_begin writes it)
   if (!r->args &&
-      upload(r->dev, nullptr, RT_QUERY_ARG_OFFSET + sizeof(rt_query_arg_t), &r->args, &args_addr))
+      upload(r->dev, nullptr, RT_SOFT_ARG_OFFSET + sizeof(rt_soft_arg_t), &r->args, &args_addr))
     return -1;
   if (rtapp::write_args(r, 0, &a, sizeof(a)) != 0)
     return fail("render argument upload failed");
@@ -2448,6 +2458,184 @@ uint32_t rt_query_key(const rt_ray_t* ray, const float box[6]) {
   float lo[3], inv[3];
   query_grid(box, lo, inv);
   return rt_query_key_of(w, lo, inv);
+}
+
+// ---- soft shadows from the visibility records (vx_rt.h; NO REFERENCE) -------
+
+int rt_renderer_soft_begin(rt_renderer_h r, const rt_soft_params_t* p) {
+  if (!r || !r->configured) return fail("renderer not configured");
+  if (!p || !p->radii) return fail("null argument");
+  if (const int e = aov_admit(r, "rt_renderer_soft_begin")) return e;
+  if ((r->params.flags & RT_RENDER_COMPACT) || r->params.shard_count > 1)
+    return fail("rt_renderer_soft_begin: a linear framebuffer only (the rays are keyed by y * W + x; compact and "
+                "sharded buffers are in task order)", -2);
+  if (!r->aov || !r->aov_launched)
+    return fail("rt_renderer_soft_begin: no visibility records since the last configure (rt_render_aov, "
+                "rt_relight_capture)", -2);
+  if (!r->set_tag || !r->set_words)
+    return fail("rt_renderer_soft_begin: the driver passes no launch tag / words (the launches' parameters)", -2);
+  const uint32_t n = r->nlights >= 2 ? r->nlights : 1u;
+  if (p->n != n)
+    return fail("rt_renderer_soft_begin: " + std::to_string(p->n) + " radii for the " + std::to_string(n) +
+                " lights in use", -2);
+  for (uint32_t i = 0; i < n; ++i)
+    if (!(p->radii[i] >= 0.0f) || std::isinf(p->radii[i]))
+      return fail("rt_renderer_soft_begin: the radius of light " + std::to_string(i) +
+                  " must be finite and >= 0, not NaN", -2);
+  if (aov_image(r, "rt_soft.vxbin", &r->soft_img) != 0 ||
+      aov_image(r, "rt_soft_resolve.vxbin", &r->soft_resolve_img) != 0)
+    return -1;
+  const uint64_t npix = r->cbuf_bytes / 4, bytes = 2 * npix * n;
+  rt_soft_arg_t sa{};
+  if (!r->soft_buf || r->soft_bytes != bytes) {
+    // the new planes first: a begin the arena cannot hold leaves the old ones, and a session on them, as
+    // they were (as every refusal above does)
+    vx_buffer_h nb = nullptr;
+    if (vx_mem_alloc(r->dev, bytes ? bytes : 64, VX_MEM_READ, &nb) != 0)
+      return fail("rt_renderer_soft_begin: the arena cannot hold " + std::to_string(bytes) + " bytes for " +
+                  std::to_string(n) + " count planes", -2);
+    if (vx_mem_address(nb, &sa.planes_addr) != 0 || sa.planes_addr + bytes > (1ull << 32)) {
+      vx_mem_free(nb);
+      return fail("rt_renderer_soft_begin: the arena cannot hold " + std::to_string(bytes) +
+                  " bytes below the 4 GiB kernel address range", -2);
+    }
+    // (not under launches still writing the old planes)
+    r->soft_on = false;
+    if (release_idle(r, &r->soft_buf) != 0) {
+      vx_mem_free(nb);
+      return -1;
+    }
+    r->soft_buf = nb;
+    r->soft_bytes = bytes;
+  } else if (vx_mem_address(r->soft_buf, &sa.planes_addr) != 0) {
+    return fail("vx_mem_address failed");
+  }
+  sa.npix = (uint32_t)npix;
+  sa.cbuf1_off = r->cbuf1_off;
+  for (uint32_t i = 0; i < n; ++i) {
+    sa.radii[i] = p->radii[i];
+    std::memcpy(sa.light[i], r->nlights >= 2 ? r->lsets[i].light : r->arg.light, sizeof(sa.light[i]));
+  }
+  // behind the launches in flight (a session before this one may still read the area), ahead of every
+  // launch started after it
+  r->soft_on = false;
+  if (rtapp::write_args(r, RT_SOFT_ARG_OFFSET, &sa, sizeof(sa)) != 0)
+    return fail("soft shadow argument upload failed");
+  r->soft_lights = n;
+  r->soft_seed = p->seed;
+  r->soft_on = true;
+  r->soft_reset = true;  // the planes are not cleared: the first launch does not read them
+  r->soft_n = 0;
+  return 0;
+}
+
+int rt_renderer_soft_reset(rt_renderer_h r) {
+  if (!r || !r->configured) return fail("renderer not configured");
+  if (!r->soft_on) return fail("rt_renderer_soft_reset: no session begun (rt_renderer_soft_begin)", -2);
+  r->soft_reset = true;
+  r->soft_n = 0;
+  return 0;
+}
+
+int rt_render_soft_start(rt_renderer_h r, uint32_t samples) {
+  if (!r || !r->configured) return fail("renderer not configured");
+  if (!r->soft_on) return fail("rt_render_soft: no session begun (rt_renderer_soft_begin)", -2);
+  if (samples < 1 || samples > RT_SOFT_MAX_S) return fail("rt_render_soft: samples must be in [1, 64]", -2);
+  if (r->soft_n + samples > RT_SOFT_MAX_SAMPLES)
+    return fail("rt_render_soft: more than 1024 samples per pixel and light (the resolve's 32-bit numerator)", -2);
+  const uint32_t lw[4] = {r->soft_seed + r->soft_n,
+                          (samples - 1u) | (r->soft_reset ? RT_SOFT_LW_RESET : 0u) |
+                              (r->soft_lights << RT_SOFT_LW_N_SHIFT),
+                          0u, 0u};
+  if (r->set_counters && r->set_counters(r->dev, (r->params.flags & RT_RENDER_COUNTERS) ? 1 : 0) != 0)
+    return fail("vx_hip_set_counters failed");
+  if (r->set_words(r->dev, lw, 4) != 0) return fail("vx_hip_set_launch_words failed");
+  if (r->set_tag(r->dev, 0) != 0) return fail("vx_hip_set_launch_tag failed");
+  // an ordinary launch (no lane asked for) on the image's own grid, as a record launch goes
+  if (vx_start(r->dev, r->soft_img, r->args) != 0) return fail("vx_start failed");
+  r->soft_n += samples;
+  r->soft_reset = false;
+  return 0;
+}
+
+int rt_render_soft(rt_renderer_h r, uint32_t samples) {
+  const int e = rt_render_soft_start(r, samples);
+  return e ? e : rt_render_wait(r);
+}
+
+int rt_renderer_soft_samples(rt_renderer_h r, uint32_t* n) {
+  if (!r || !n) return fail("null argument");
+  if (!r->configured || !r->soft_on)
+    return fail("rt_renderer_soft_samples: no session begun (rt_renderer_soft_begin)", -2);
+  *n = r->soft_n;
+  return 0;
+}
+
+int rt_read_soft(rt_renderer_h r, uint16_t* out, uint64_t count) {
+  if (!r || !out || !r->configured) return fail("renderer not configured");
+  if (!r->soft_on) return fail("rt_read_soft: no session begun (rt_renderer_soft_begin)", -2);
+  if (r->soft_n == 0) return fail("rt_read_soft: no sample traced since the last begin / reset (rt_render_soft)", -2);
+  if (count * 2 < r->soft_bytes) return fail("buffer too small");
+  return (r->soft_bytes == 0 || vx_copy_from_dev(out, r->soft_buf, 0, r->soft_bytes) == 0)
+             ? 0 : fail("vx_copy_from_dev failed");
+}
+
+int rt_render_soft_resolve_start(rt_renderer_h r, uint32_t mode, const uint8_t* weights, uint32_t n) {
+  if (!r || !r->configured) return fail("renderer not configured");
+  if (!r->soft_on) return fail("rt_render_soft_resolve: no session begun (rt_renderer_soft_begin)", -2);
+  if (r->soft_n == 0)
+    return fail("rt_render_soft_resolve: no sample traced since the last begin / reset (N = 0)", -2);
+  if (mode != RT_SOFT_LIT && mode != RT_SOFT_GREY) return fail("rt_render_soft_resolve: unknown mode", -2);
+  // unit weights: every light in use one
+  uint32_t lw[4] = {0, 0, 0, 0};
+  std::memset(lw, 1, r->soft_lights);
+  if (mode == RT_SOFT_LIT) {
+    if (r->relight_n == 0)
+      return fail("rt_render_soft_resolve: RT_SOFT_LIT without a relight capture since the last configure / "
+                  "set_light / set_lights (rt_relight_capture)", -2);
+    if (weights) {
+      if (n != r->soft_lights)
+        return fail("rt_render_soft_resolve: " + std::to_string(n) + " weights for the session's " +
+                    std::to_string(r->soft_lights) + " lights", -2);
+      uint32_t W = 0;
+      lw[0] = lw[1] = lw[2] = lw[3] = 0;
+      std::memcpy(lw, weights, n);
+      for (uint32_t i = 0; i < n; ++i) W += weights[i];
+      if (W == 0) return fail("rt_render_soft_resolve: every weight is 0", -2);
+    }
+  }
+  // into the framebuffer in use, as a relight launch goes: no flip, no lane
+  const int buf = r->cur_buf < 0 ? 0 : r->cur_buf;
+  const uint32_t tag = r->soft_lights | (buf ? RT_SOFT_TAG_CBUF1 : 0u) | (mode == RT_SOFT_LIT ? RT_SOFT_TAG_LIT : 0u) |
+                       (r->soft_n << RT_SOFT_TAG_SAMPLES_SHIFT);
+  // (the launch counts nothing: no counter rows)
+  if (r->set_counters && r->set_counters(r->dev, 0) != 0) return fail("vx_hip_set_counters failed");
+  if (r->set_words(r->dev, lw, 4) != 0) return fail("vx_hip_set_launch_words failed");
+  if (r->set_tag(r->dev, tag) != 0) return fail("vx_hip_set_launch_tag failed");
+  if (vx_start(r->dev, r->soft_resolve_img, r->args) != 0) return fail("vx_start failed");
+  r->prev_buf = -1;
+  r->cur_buf = buf;
+  return 0;
+}
+
+int rt_render_soft_resolve(rt_renderer_h r, uint32_t mode, const uint8_t* weights, uint32_t n) {
+  const int e = rt_render_soft_resolve_start(r, mode, weights, n);
+  return e ? e : rt_render_wait(r);
+}
+
+uint32_t rt_soft_resolve(uint32_t base_argb, uint32_t depth_flags, const uint16_t* counts, uint32_t N,
+                         const uint8_t* weights, uint32_t n) {
+  if (!counts || !weights || N == 0 || N > RT_SOFT_MAX_SAMPLES || n < 1 || n > RT_MAX_LIGHTS) return base_argb;
+  uint32_t W = 0, O = 0;
+  for (uint32_t i = 0; i < n; ++i) {
+    W += weights[i];
+    O += weights[i] * (counts[i] < N ? counts[i] : N);
+  }
+  // (the resolve launch does not read the flag: it relies on the tracing launch having stored 0 for every
+  // pixel that is not a ray pixel, and O = 0 gives the base colour back -- the same pixel either way)
+  if (W == 0 || !(depth_flags & RT_AOV_GEOM)) return base_argb;
+  const uint32_t D = N * W;
+  return rt_soft_mix(base_argb, O, D, 1.0f / (float)(2u * D));
 }
 
 // ---- denoising accumulated path frames (vx_rt.h; NO REFERENCE) -------------

@@ -149,6 +149,16 @@ struct rt_renderer {
   bool ao_reset = false;      // the next tracing launch carries RT_AO_LW_RESET
   uint32_t ao_n = 0;          // samples queued since the last reset: the counts' N once they ran
   rt_ao_params_t ao_params{};
+  // soft shadows (vx_rt.h rt_renderer_soft_begin / rt_render_soft_start / rt_render_soft_resolve_start):
+  // the rt_soft and rt_soft_resolve images, loaded and kept the same way, and the count planes of the
+  // session (rt_common.h rt_soft_arg_t: 2 B per light in use and framebuffer pixel)
+  vx_buffer_h soft_img = nullptr, soft_resolve_img = nullptr, soft_buf = nullptr;
+  uint64_t soft_bytes = 0;
+  bool soft_on = false;        // between soft_begin and the next configure or change of lights
+  bool soft_reset = false;     // the next tracing launch carries RT_SOFT_LW_RESET
+  uint32_t soft_n = 0;         // samples queued since the last reset: the counts' N once they ran
+  uint32_t soft_lights = 0;    // the session's lights
+  uint32_t soft_seed = 0;
   // caller-supplied rays (vx_rt.h rt_query_reserve / rt_query_trace_start / rt_query_keys_start): the
   // rt_query and rt_query_keys images, loaded and kept the same way, and the one buffer of the reserve
   // (rt_common.h rt_query_arg_t: rays, hits, skip words, permutation and keys, 52 B per ray) -- kept
@@ -278,7 +288,7 @@ struct rt_renderer {
                            &cbuf, &cbuf1, &args, &verts, &pdc, &dcz, &layer_list, &geometry_list, &vis,
                            &blist, &bidx, &btrim, &btidx, &btrim_img, &btrim_args, &cdesc, &bglayer, &sidx, &slist, &pathq, &pathq_ctr, &oidx, &olist, &ovtris,
                            &accum, &aov, &aov_img, &relight_base, &aov_base_img, &relight_img,
-                           &dn_guide_img, &dn_prep_img, &dn_pass_img, &dn_buf, &ao_img, &ao_resolve_img, &ao_buf,
+                           &dn_guide_img, &dn_prep_img, &dn_pass_img, &dn_buf, &ao_img, &ao_resolve_img, &ao_buf, &soft_img, &soft_resolve_img, &soft_buf,
                            &q_img, &q_keys_img, &q_buf};
     for (auto* b : bufs) {
       if (*b) vx_mem_free(*b);

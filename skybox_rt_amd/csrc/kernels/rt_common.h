@@ -603,6 +603,57 @@ static inline uint32_t rt_query_key_of(const uint32_t w[8], const float lo[3], c
   const uint32_t cy = (uint32_t)__builtin_fminf((a[1] / s) * 16.0f, 15.0f);
   return key | (cy << 4) | cx;
 }
+// Soft shadows from area lights, sampled from the visibility records (vx_rt.h rt_renderer_soft_begin /
+// rt_render_soft_start / rt_render_soft_resolve_start).  The tracing launch (rt_soft_kernel.hip, image
+// rt_soft) reads the record buffer of rt_aov_arg_t and adds, per light in use and framebuffer pixel, its
+// occluded samples to one uint16 of the count planes (plane i at planes_addr + 2 * npix * i); the resolve
+// launch (rt_soft_resolve_kernel.hip, image rt_soft_resolve) streams the planes and the relight capture's
+// base colours into the framebuffer in use.  Their argument area, behind the nine above, which stay where
+// they are: written by rt_renderer_soft_begin in stream order, constant until the session ends.  The
+// lights' positions stand beside their radii: a session's lights do not move (a call that changes the
+// lights ends it), and one light and several reach a frame by different roads (the launch words, the light
+// table) which this launch need not follow.  Linear W * H framebuffers only.
+typedef struct {
+  uint64_t planes_addr;             // the count planes, uint16 [n][npix]
+  uint32_t npix;                    // framebuffer pixels
+  uint32_t cbuf1_off;               // the second framebuffer past arg.cbuf_addr, mod 2^32 (RT_SOFT_TAG_CBUF1)
+  float radii[RT_MAX_LIGHTS];       // light i's radius, finite and >= 0
+  float light[RT_MAX_LIGHTS][3];    // light i's centre
+} rt_soft_arg_t;
+#define RT_SOFT_ARG_OFFSET (RT_QUERY_ARG_OFFSET + sizeof(rt_query_arg_t))
+// A tracing launch's words: w[0] = seed + the sample cursor of the launch's first sample (mod 2^32), w[1] =
+// the bits below, w[2] = w[3] = 0 (a frame's flags: none)
+#define RT_SOFT_LW_S_MASK  0x3fu      // bits 0-5: the launch's samples per ray pixel and light minus one (1..64)
+#define RT_SOFT_LW_RESET   0x40u      // bit 6: the launch treats every count as zero and does not read it
+#define RT_SOFT_LW_N_SHIFT 8          // bits 8-12: the lights in use, 1..RT_MAX_LIGHTS
+#define RT_SOFT_MAX_S 64u
+#define RT_SOFT_MAX_SAMPLES 1024u     // the sample cursor's cap: 511 * N * sum w <= 511 * 1024 * 4080 < 2^32
+#define RT_SOFT_VERTEX 64u            // light i's samples are keyed at path vertex RT_SOFT_VERTEX + i
+// A resolve launch's words are its 16 weight bytes (as a relight launch's); its tag:
+#define RT_SOFT_TAG_N_MASK 0x1fu      // bits 0-4: the session's lights, 1..RT_MAX_LIGHTS
+#define RT_SOFT_TAG_CBUF1  0x20u      // bit 5: the framebuffer in use is the second one
+#define RT_SOFT_TAG_LIT    0x40u      // bit 6: RT_SOFT_LIT (the capture's base colours), else RT_SOFT_GREY (white)
+#define RT_SOFT_TAG_SAMPLES_SHIFT 8   // bits 8-18: N, the samples in the counts, 1..1024
+// The soft-shadow pixel (vx_rt.h rt_soft_resolve): D = N * sum w_i, O = sum w_i * o_i (o_i <= N) <= D; per
+// colour channel c of base (2 * ((D - O) * c + O * (c >> 1)) + D) / (2 * D) in integer division, the
+// relight mean with every light's weight split over its N samples, under base's alpha byte.  The numerator
+// is at most 2 * 255 * D + D = 511 * D <= 511 * 1024 * 4080 = 2 134 917 120 < 2^32.  The division is
+// rt_ao_quot's, whose argument holds for this divisor too: d = 2 * D < 2^23 is exact in binary32, x <= 255.5
+// * d, the estimate (float)x * rd lies within 256 * 3 * 2^-24 < 2^-14 of x / d, and q * d <= 256 * 2^23 =
+// 2^31 with a remainder below 2 * d < 2^24 in magnitude.  rd = 1.0f / (float)(2 * D).  O = 0 gives c back: a
+// pixel that is not a ray pixel, whose counts are 0, keeps its base colour.  The kernel and the host share
+// this text.
+#if defined(__HIPCC__)
+__host__ __device__
+#endif
+static inline uint32_t rt_soft_mix(uint32_t base, uint32_t O, uint32_t D, float rd) {
+  uint32_t out = base & 0xff000000u;
+  for (int sh = 0; sh <= 16; sh += 8) {
+    const uint32_t c = (base >> sh) & 0xffu;
+    out |= rt_ao_quot(2u * ((D - O) * c + O * (c >> 1)) + D, 2u * D, rd) << sh;
+  }
+  return out;
+}
 // A path-traced frame lit by several point lights (pt_kernel.hip PT_LIGHTS, images pt_lights /
 // pt_lights_accum; vx_rt.h rt_renderer_set_path_lights) reads the first count <=
 // RT_MAX_PATH_LIGHTS entries of the same table, every one with lists (slist_on 1).  The cap is

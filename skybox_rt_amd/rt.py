@@ -103,6 +103,16 @@ class AoParams(C.Structure):
     _fields_ = [("radius", C.c_float), ("seed", C.c_uint32)]
 
 
+# soft shadows (vx_rt.h rt_soft_params_t, RT_SOFT_DEFAULT_SEED, RT_SOFT_LIT / RT_SOFT_GREY)
+RT_SOFT_DEFAULT_SEED = 0x5EED
+RT_SOFT_MAX_SAMPLES = 1024
+SOFT_MODES = {"lit": 0, "grey": 1}
+
+
+class SoftParams(C.Structure):
+    _fields_ = [("radii", C.POINTER(C.c_float)), ("n", C.c_uint32), ("seed", C.c_uint32)]
+
+
 # caller-supplied rays (vx_rt.h rt_ray_t / rt_hit_t / rt_query_buffers_t, RT_QUERY_*)
 RAY_DTYPE = np.dtype([("o", "<f4", 3), ("tmin", "<f4"), ("d", "<f4", 3), ("tmax", "<f4")])
 HIT_DTYPE = np.dtype([("pid", "<i4"), ("t", "<f4")])
@@ -225,6 +235,14 @@ def lib():
             "rt_read_ao": [vp, vp, u64],
             "rt_render_ao_resolve_start": [vp, u32, vp, u32],
             "rt_render_ao_resolve": [vp, u32, vp, u32],
+            "rt_renderer_soft_begin": [vp, C.POINTER(SoftParams)],
+            "rt_renderer_soft_reset": [vp],
+            "rt_render_soft_start": [vp, u32],
+            "rt_render_soft": [vp, u32],
+            "rt_renderer_soft_samples": [vp, C.POINTER(u32)],
+            "rt_read_soft": [vp, vp, u64],
+            "rt_render_soft_resolve_start": [vp, u32, vp, u32],
+            "rt_render_soft_resolve": [vp, u32, vp, u32],
             "rt_query_reserve": [vp, u64],
             "rt_query_buffers": [vp, C.POINTER(QueryBuffers)],
             "rt_query_write_rays": [vp, vp, u64, u64],
@@ -253,6 +271,8 @@ def lib():
         h.rt_relight_resolve.restype = u32
         h.rt_ao_resolve.argtypes = [u32, u32, u32]
         h.rt_ao_resolve.restype = u32
+        h.rt_soft_resolve.argtypes = [u32, u32, vp, u32, vp, u32]
+        h.rt_soft_resolve.restype = u32
         h.rt_query_key.argtypes = [vp, C.POINTER(C.c_float)]
         h.rt_query_key.restype = u32
         h.rt_last_error.restype = C.c_char_p
@@ -911,6 +931,65 @@ class Renderer:
         _check(lib().rt_query_read_hits(self._h, out.ctypes.data, 0, int(n)), "rt_query_read_hits")
         return out["pid"].copy(), out["t"].copy()
 
+    # soft shadows from the records (vx_rt.h rt_renderer_soft_begin; images rt_soft, rt_soft_resolve)
+    def soft_begin(self, radii, seed: int = RT_SOFT_DEFAULT_SEED) -> None:
+        """Begin a soft-shadow session on the visibility records of the last aov() /
+        relight_capture(): one radius (finite, >= 0) per light in use, sample c keyed
+        by seed + c.  Linear framebuffers only.  configure(), set_light(),
+        set_lights() and set_path_lights() end it; a refused begin leaves a session
+        already begun as it was."""
+        rad = np.ascontiguousarray(np.atleast_1d(np.asarray(radii, np.float32)))
+        if rad.ndim != 1 or rad.size == 0:
+            raise RtError("rt_renderer_soft_begin failed: radii is one float per light")
+        p = SoftParams(rad.ctypes.data_as(C.POINTER(C.c_float)), rad.size, int(seed) & 0xFFFFFFFF)
+        _check(lib().rt_renderer_soft_begin(self._h, C.byref(p)), "rt_renderer_soft_begin")
+        self._soft_n = int(rad.size)
+
+    def soft_reset(self) -> None:
+        """The sample cursor back to 0; the next soft() launch overwrites the counts."""
+        _check(lib().rt_renderer_soft_reset(self._h), "rt_renderer_soft_reset")
+
+    def soft(self, samples: int, wait: bool = True) -> None:
+        """One launch tracing `samples` (1..64) more segments per ray pixel and light
+        -- to cosine-weighted points of the light's sphere that face the pixel --
+        and adding the occluded ones to the (light, pixel) count (soft_records()).
+        It writes neither the framebuffer nor the visibility records."""
+        fn = lib().rt_render_soft if wait else lib().rt_render_soft_start
+        _check(fn(self._h, int(samples)), "rt_render_soft" if wait else "rt_render_soft_start")
+
+    def soft_samples(self) -> int:
+        """N: the samples traced per ray pixel and light since soft_begin() / soft_reset()."""
+        n = C.c_uint32()
+        _check(lib().rt_renderer_soft_samples(self._h, C.byref(n)), "rt_renderer_soft_samples")
+        return int(n.value)
+
+    def soft_records(self) -> np.ndarray:
+        """The occluded samples per light and pixel, uint16 [n, H, W] (waits for the device)."""
+        p = self.params
+        if p is None:
+            raise RtError("rt_read_soft failed: renderer not configured")
+        out = np.zeros((max(getattr(self, "_soft_n", 1), 1), p.height, p.width), np.uint16)
+        _check(lib().rt_read_soft(self._h, out.ctypes.data, out.size), "rt_read_soft")
+        return out
+
+    def soft_resolve(self, mode: str = "lit", weights=None, wait: bool = True) -> None:
+        """One streaming launch writing the soft-shadow term into the framebuffer in
+        use: mode "lit" rt.soft_resolve over the base colours of the live
+        relight_capture() under `weights` (one 0..255 per light; None: unit weights);
+        "grey" the term on white under unit weights."""
+        if mode not in SOFT_MODES:
+            raise RtError(f"rt_render_soft_resolve failed: mode is one of {sorted(SOFT_MODES)}")
+        wp, n = None, 0
+        if weights is not None:
+            w = np.asarray(weights)
+            if w.ndim != 1 or w.size == 0 or (w < 0).any() or (w > 255).any():
+                raise RtError("rt_render_soft_resolve failed: weights are 0..255, one per light")
+            w = np.ascontiguousarray(w, np.uint8)
+            wp, n = w.ctypes.data, w.size
+        fn = lib().rt_render_soft_resolve if wait else lib().rt_render_soft_resolve_start
+        _check(fn(self._h, SOFT_MODES[mode], wp, n),
+               "rt_render_soft_resolve" if wait else "rt_render_soft_resolve_start")
+
     # denoising accumulated path frames (vx_rt.h rt_denoise_capture_start; images rt_aov_guide,
     # rt_denoise_prep, rt_denoise_pass)
     def denoise_capture(self, wait: bool = True) -> None:
@@ -1201,6 +1280,35 @@ def query_key(ray, box):
     for i in range(len(c)):
         out[i] = fn(base + 32 * i, b)
     return out
+
+
+def soft_resolve(base_argb, depth_flags, counts, n_samples: int, weights):
+    """rt_soft_resolve: the soft-shadow pixel -- with D = n_samples * sum(weights) and
+    O = sum(weights[i] * min(counts[i], n_samples)), per colour channel c of base_argb
+    (2 * ((D - O) * c + O * (c >> 1)) + D) // (2 * D) under base_argb's alpha byte for
+    a pixel with RT_AOV_GEOM, base_argb for any other.  counts is [n] or [n, ...]
+    (a plane per light), weights one 0..255 per light.  Scalars give an int; arrays
+    (broadcast against each other) a uint32 array, the library's function applied to
+    every distinct (pixel, geometry bit, counts) row."""
+    fn = lib().rt_soft_resolve
+    w = np.ascontiguousarray(np.asarray(weights), np.uint8).reshape(-1)
+    cnt = np.asarray(counts).astype(np.uint16)
+    if cnt.shape[0] != w.size:
+        raise RtError("rt_soft_resolve failed: one count plane per weight")
+    N, n = int(n_samples), int(w.size)
+    if np.ndim(base_argb) == 0 and np.ndim(depth_flags) == 0 and cnt.ndim == 1:
+        c = np.ascontiguousarray(cnt)
+        return int(fn(int(base_argb) & 0xFFFFFFFF, int(depth_flags) & 0xFFFFFFFF, c.ctypes.data, N, w.ctypes.data, n))
+    a, f = np.broadcast_arrays(np.asarray(base_argb).astype(np.uint32), np.asarray(depth_flags).astype(np.uint32))
+    planes = np.ascontiguousarray(np.broadcast_to(cnt.reshape((n,) + cnt.shape[1:]), (n,) + a.shape)).reshape(n, -1)
+    rows = np.concatenate([a.reshape(1, -1).astype(np.uint64), (f.reshape(1, -1) & RT_AOV_GEOM).astype(np.uint64),
+                           planes.astype(np.uint64)], 0).T
+    uniq, inv = np.unique(rows, axis=0, return_inverse=True)
+    vals = np.empty(len(uniq), np.uint32)
+    for k, u in enumerate(uniq):
+        c = np.ascontiguousarray(u[2:], np.uint16)
+        vals[k] = fn(int(u[0]), int(u[1]), c.ctypes.data, N, w.ctypes.data, n)
+    return vals[np.asarray(inv).reshape(-1)].reshape(a.shape)
 
 
 def path_lights_resolve(sums, k: int, alpha_argb: int) -> int:
