@@ -848,6 +848,29 @@ __device__ __forceinline__ uint32_t slist_cell(const Ray& s, uint32_t N) {
 __device__ __forceinline__ float slist_limit(const Ray& s) {
   return (s.d[0] * s.d[0] + s.d[1] * s.d[1] + s.d[2] * s.d[2]) * 1.001f;
 }
+// RT_SLIST_BATCH (per image): how a round of the per-lane scans below issues its
+// record loads.  The source asks for the round's six 16-byte loads together, but the compiler sinks
+// each row behind the early-out branch in front of its first use, so a round makes three dependent
+// vector round trips (record 0's e1 | key row; its v0 | pid row and record 1; its e2 row).
+//   0  the code as the compiler schedules it (the default: every image that does not name the knob)
+//   1  the six loads issued together, one wait behind them: slist_pin holds the rows in VGPRs at the
+//      loads, so no load can move behind a branch -- one trip a round
+// Arithmetic, record order, bounds, counters and the padding record read past an odd list are the
+// same in both.  (The two e1 | key rows first and the other four behind record 0's bound -- two trips,
+// fewer bytes for a lane that stops on a key -- missed the images' register budgets and is not kept:
+// DESIGN.md.  The next round's loads under this round's tests: 24 more VGPRs, not built.)
+#ifndef RT_SLIST_BATCH
+#define RT_SLIST_BATCH 0
+#endif
+#if RT_SLIST_BATCH
+// (an empty statement the rows' words pass through as VGPRs: it emits nothing, and the compiler must
+// have every row loaded in front of it)
+#define RT_SLIST_ROW(r) "+v"((r).x), "+v"((r).y), "+v"((r).z), "+v"((r).w)
+__device__ __forceinline__ void slist_pin(float4* t) {  // a round's six rows
+  asm volatile("" : RT_SLIST_ROW(t[0]), RT_SLIST_ROW(t[1]), RT_SLIST_ROW(t[2]), RT_SLIST_ROW(t[3]),
+                    RT_SLIST_ROW(t[4]), RT_SLIST_ROW(t[5]));
+}
+#endif
 // (the lists of one light: their index and entries, at slist_n cells per face side -- a light of
 // the table behind the argument block, or, the overload below, the scene's own)
 // (the scan of a cell's n records from record `off` on: occluded_list's second half, and
@@ -860,6 +883,9 @@ __device__ __forceinline__ bool slist_scan(const Scene& S, const Ray& s, int32_t
     float4 t[6];
 #pragma unroll
     for (int w = 0; w < 6; ++w) t[w] = S.A.ld_f4(o + 16u * w);  // 2 records (a padding one at the end)
+#if RT_SLIST_BATCH
+    slist_pin(t);
+#endif
 #pragma unroll
     for (int e = 0; e < 2; ++e) {
       if (q + e >= n) break;
@@ -877,7 +903,15 @@ __device__ __forceinline__ bool occluded_list(const Scene& S, const Ray& s, bool
                                               Counters& cnt, uint32_t sidx, uint32_t slist, uint32_t slist_n) {
   if (!act) return false;
   const uint32_t cell = slist_cell(s, slist_n);
+#if RT_SLIST_BATCH
+  // (the header's two words held at their loads: the compiler sinks `off` behind the test of n, a
+  // second round trip in front of the scan; held, they merge into one 8-byte load.  ld_u2, as
+  // rt_kernel.hip's fused_header takes it, costs that image a VGPR spill here)
+  uint32_t off = S.A.ld_u32(sidx + 8u * cell), n = S.A.ld_u32(sidx + 8u * cell + 4u);
+  asm volatile("" : "+v"(off), "+v"(n));
+#else
   const uint32_t off = S.A.ld_u32(sidx + 8u * cell), n = S.A.ld_u32(sidx + 8u * cell + 4u);
+#endif
   return slist_scan(S, s, skip, cnt, slist, off, n);
 }
 __device__ __forceinline__ bool occluded_list(const Scene& S, const Ray& s, bool act, int32_t skip,
@@ -1176,7 +1210,12 @@ __device__ __forceinline__ bool occluded_list_coop(const Scene& S, const Ray& s,
                                                    uint32_t slist_n) {
   if (!act) return false;
   const uint32_t cell = slist_cell(s, slist_n);
+#if RT_SLIST_BATCH  // (occluded_list's)
+  uint32_t off = S.A.ld_u32(sidx + 8u * cell), n = S.A.ld_u32(sidx + 8u * cell + 4u);
+  asm volatile("" : "+v"(off), "+v"(n));
+#else
   const uint32_t off = S.A.ld_u32(sidx + 8u * cell), n = S.A.ld_u32(sidx + 8u * cell + 4u);
+#endif
   const uint32_t e0 = hi ? 2u : 0u;
   const float lim = slist_limit(s);
   uint32_t o = slist + 48u * (off + e0);
@@ -1187,6 +1226,9 @@ __device__ __forceinline__ bool occluded_list_coop(const Scene& S, const Ray& s,
       float4 t[6];
 #pragma unroll
       for (int w = 0; w < 6; ++w) t[w] = S.A.ld_f4(o + 16u * w);
+#if RT_SLIST_BATCH  // (slist_scan's)
+      slist_pin(t);
+#endif
 #pragma unroll
       for (uint32_t e = 0; e < 2; ++e) {
         if (!hit && !end && q + e0 + e < n) {
